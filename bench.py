@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the crossover scoring pass on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c2] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One *step* = one primal-dual indicator scoring pass of ``get_perturb_problem``
@@ -21,9 +21,12 @@ Workload (weak scaling): rank r owns column block r (m x n_block, CSC) and row b
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with ``roofline`` for the walk that takes
 the largest share of the step (K1, K2 and K10 are all timed with HIP events inside the timed region and
-reported under ``kernels``), ``roofline_uniform`` (the same three walks on the no-locality variant of the
-workload, N = 1 only), ``cpu_baseline`` (the numpy/scipy oracle timed on the host cores, rank 0, N = 1 only)
-and ``crossover`` (wall times of whole crossovers through the drop-in API).
+reported under ``kernels``).  A plain run sets up, warms up, times the steps, writes the last step's outputs
+when ``--dump-outputs DIR`` is given, and prints the line.  ``--full`` adds the legs that take runs of their
+own: ``roofline_uniform`` (the same three walks on the no-locality variant of the workload, N = 1 only),
+``cpu_baseline`` (the numpy/scipy oracle timed on the host cores and checked against the timed pass, rank 0,
+N = 1 only), ``crossover`` (wall times of whole crossovers through the drop-in API), ``sharded_pricing`` and,
+at N > 1, ``sharded_resolve``; without it these keys are null.
 """
 import argparse
 import json
@@ -129,7 +132,7 @@ def crossover_lp_end_to_end(highs_limit_s: float, cpu_path_s: float = 0.0):
         import glob
         for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", "lp_c2_highs.json")), reverse=True):
             cpu = json.load(open(path))
-            cpu["recorded_in"] = os.path.relpath(path, ROOT) + " (python bench.py --highs-seconds SECONDS re-measures it)"
+            cpu["recorded_in"] = os.path.relpath(path, ROOT) + " (python bench.py --full --highs-seconds SECONDS re-measures it)"
             rec["cpu"] = cpu
             key = "ratio_vs_recorded_cpu_other_host_resolve"
             if cpu.get("cpu_resolve_status") != "OPTIMAL":
@@ -208,7 +211,7 @@ def _cpu_path_record(name: str, which: dict, limit_s: float, objective: float, g
         import glob
         for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", name)), reverse=True):
             rec = json.load(open(path))
-            rec["recorded_in"] = os.path.relpath(path, ROOT) + " (bench.py --lp-cpu-path SECONDS re-measures it)"
+            rec["recorded_in"] = os.path.relpath(path, ROOT) + " (bench.py --full --lp-cpu-path SECONDS re-measures it)"
             break
     if rec is None:
         return None
@@ -301,7 +304,7 @@ def crossover_lp_1e6(lp_highs_s: float, cpu_path_s: float = 0.0):
         import glob
         for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", "lp_1e6_highs.json")), reverse=True):
             cpu = json.load(open(path))
-            cpu["recorded_in"] = os.path.relpath(path, ROOT) + " (python bench.py --lp-highs SECONDS re-measures it)"
+            cpu["recorded_in"] = os.path.relpath(path, ROOT) + " (python bench.py --full --lp-highs SECONDS re-measures it)"
             break
     if cpu is not None:
         rec["cpu"] = cpu
@@ -508,6 +511,32 @@ def crossover_mcf(V: int = 4096, E: int = 32768, solvers=("HIP", "HGS"), repeats
     return out
 
 
+DUMP_SAMPLE = 1 << 19      # elements kept of an output longer than this (at most 4 MiB per file, 9 files)
+
+
+def dump_outputs(out_dir: str, counts, vectors: dict, index_sets: dict, price_record):
+    """``--dump-outputs``: what a caller of the timed step receives, as it stands in HBM after the last timed step --
+    the dense results (s_d, code, s_p, flag), each index set up to the size the step counted for it, the three
+    sizes and the pricing record (min reduced cost, its column, number of violating columns).  One
+    ``<name>.npy`` each: float64, byte codes / flags as float32 (exact).  An array longer than DUMP_SAMPLE is written
+    as its elements at DUMP_SAMPLE ascending positions drawn with a fixed seed, so that two builds run with the same
+    arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def write(name, a):
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(2024).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if a.dtype == np.uint8 else np.float64))
+
+    sizes = counts.download()
+    for name, d in vectors.items():
+        write(name, d.download())
+    for (name, d), size in zip(index_sets.items(), sizes):
+        write(name, d.download(int(size)))
+    write("set_sizes", sizes)
+    write("price", np.array(price_record, dtype=np.float64))
+
+
 def _heartbeat():
     """One stderr line a minute while the long legs (HiGHS beside the device crossover) run: a driver that takes
     minutes of silence for a hang sees progress.  stdout stays the single JSON line."""
@@ -534,6 +563,14 @@ def main():
     ap.add_argument("--workload", default="c5", choices=sorted(WORKLOADS))
     ap.add_argument("--structure", default=None, choices=["staircase", "uniform"],
                     help="row structure of the synthetic LP (default: staircase = netlib-style for c5, uniform for c2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (this rank's s_d, code, s_p, flag, the three "
+                         "index sets and their sizes, the pricing record) as DIR/<name>.npy, float64 / float32; arrays longer "
+                         "than 2^19 as a fixed, seeded sample of their elements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: no-locality record, CPU baseline and its parity check, "
+                         "whole crossovers, sharded pricing rounds and (N > 1) the sharded re-solve; the --no-* and size options "
+                         "below choose among them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget for the CPU baseline sample")
     ap.add_argument("--no-crossover", action="store_true", help="skip the whole-crossover timings")
@@ -565,6 +602,11 @@ def main():
                          "simplex, this HiGHS time limit in seconds) beside the two LP crossovers in this run and write "
                          "gpurun_out/lp_1e6_cpu_path.json / lp_c2_cpu_path.json (0: quote the records under profiles/)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:       # a plain run: set-up, warm-up, the timed steps, the outputs, the line
+        args.no_cpu_baseline = args.no_crossover = args.no_uniform = True
+        args.pricing_rounds = args.resolve_rows = 0
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -712,6 +754,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, counts, {"s_d": s_d, "code": code, "s_p": s_p, "flag": flag},
+                     {"fix_low": idx_low, "fix_up": idx_up, "fixed_rows": idx_row}, ctx.read_price(price))
 
     # ---- pricing rounds of a column-sharded simplex pivot (ShardedLP.simplex_price): K10 over the rank's column block
     # + ONE all-gather of the 24-byte records; the rest of a pivot (FTRAN, ratio test, update) is replicated
@@ -984,7 +1030,7 @@ def main():
                 rec = json.loads(open(rec_path).readline())
                 net_c4["host_solver_ms_recorded"] = rec["wall_ms"]
                 net_c4["simplex_iterations_HGS_recorded"] = rec["simplex_iterations"]
-                net_c4["recorded_in"] = "profiles/r02/netdual_c4_highs.jsonl (python bench.py --c4-highs re-measures it)"
+                net_c4["recorded_in"] = "profiles/r02/netdual_c4_highs.jsonl (python bench.py --full --c4-highs re-measures it)"
                 if abs(rec["cost"] - net_c4["optimal_cost"]) > 1e-9 * (1 + abs(rec["cost"])):
                     raise SystemExit("bench: the device's config-4 optimum differs from the recorded HiGHS optimum")
         crossover = {"lp_1e6_end_to_end": crossover_lp_1e6(args.lp_highs, args.lp_cpu_path),

@@ -62,7 +62,7 @@ def test_sharded_lp_and_mcf_with_the_real_kernels(tmp_path):
     check_sharded_results(res)
 
 
-def test_bench_n_gt_1_code_path_over_rccl_with_one_rank():
+def test_bench_n_gt_1_code_path_over_rccl_with_one_rank(tmp_path):
     """``bench.py``'s N > 1 path over RCCL itself, as far as a box with one GPU allows: one rank under
     torch.distributed.run with SX_BENCH_REHEARSAL=rccl1 -- process group "nccl" on the device, kernels and
     collectives on one stream, the all-gather of the 48-byte records, barrier, MAX all-reduce of the time and the
@@ -71,17 +71,28 @@ def test_bench_n_gt_1_code_path_over_rccl_with_one_rank():
     common = ["--gpus", "1", "--workload", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-crossover",
               "--no-uniform"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    plain = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, env=env, capture_output=True,
-                           timeout=600, cwd=root)
+    plain = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + ["--dump-outputs", str(tmp_path / "out")],
+                           env=env, capture_output=True, timeout=600, cwd=root)
     assert plain.returncode == 0, plain.stderr.decode(errors="replace")[-2000:]
     env["SX_BENCH_REHEARSAL"] = "rccl1"
     dist = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py")]
-                          + common + ["--cg-iters", "5", "--resolve-rows", "4000"], env=env, capture_output=True, timeout=600, cwd=root)
+                          + common + ["--full", "--cg-iters", "5", "--resolve-rows", "4000"], env=env, capture_output=True, timeout=600, cwd=root)
     assert dist.returncode == 0, dist.stderr.decode(errors="replace")[-2000:]
     a = json.loads(plain.stdout.decode().strip().splitlines()[-1])
     b = json.loads(dist.stdout.decode().strip().splitlines()[-1])
     assert a["result"] == b["result"] and b["result"]["fix_low"] > 0
+    # a run without --full times the step only; --dump-outputs wrote what its last step computed
+    assert a["steps"] == 3 and a["ms_per_step"] > 0 and a["cpu_baseline"] is None and a["crossover"] is None
+    import numpy as np
+    dump = {f.stem: np.load(f) for f in (tmp_path / "out").iterdir()}
+    assert all(v.dtype in (np.float32, np.float64) for v in dump.values())
+    assert [int(v) for v in dump["set_sizes"]] == [a["result"][k] for k in ("fix_low", "fix_up", "fixed_rows")]
+    assert dump["s_d"].size == dump["code"].size == 100_000 and dump["s_p"].size == dump["flag"].size == 20_000
+    for k in ("fix_low", "fix_up", "fixed_rows"):
+        assert dump[k].size == a["result"][k] and np.all(np.diff(dump[k]) > 0)
+    assert np.array_equal(np.flatnonzero(dump["code"].astype(np.int64) & 1), dump["fix_low"])
+    assert dump["price"].tolist() == [a["result"]["min_rc"], a["result"]["argmin"], a["result"]["n_violating"]]
     assert b["n_gpus"] == 1 and b["sharded_cg"]["iterations"] == 5
     # the column-sharded re-solve leg went over RCCL too (record counts, records, entering columns) and reached the optimum
     rs = b["sharded_resolve"]

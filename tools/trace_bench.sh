@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/trace_bench
 rm -rf $OUT && mkdir -p $OUT
-rocprofv3 --kernel-trace --stats -d $OUT/raw --output-format csv -- python3 $R/bench.py --no-crossover --no-cpu-baseline $EXTRA > $OUT/bench_line_under_rocprof.json 2> $OUT/stderr.log
+rocprofv3 --kernel-trace --stats -d $OUT/raw --output-format csv -- python3 $R/bench.py --full --no-crossover --no-cpu-baseline $EXTRA > $OUT/bench_line_under_rocprof.json 2> $OUT/stderr.log
 find $OUT/raw -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_bench_c5.csv \;
 rm -rf $OUT/raw
 head -12 $OUT/kernel_stats_bench_c5.csv
