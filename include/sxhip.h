@@ -289,6 +289,33 @@ int sx_spanning_tree_ot_dev(sx_ctx *ctx, int64_t S, int64_t D, const double *w, 
  * index (== np.argsort(key, kind="stable")[::-1]); NaN ranks first.  idx_out: n int64.  Blocking. */
 int sx_argsort_desc_dev(sx_ctx *ctx, int64_t n, const double *key, int64_t *idx_out);
 
+/* ------------------------------------------------------------------ K17: column norms and the norm-scaled indicator
+ * An optional extra WITHOUT a reference counterpart (the reference has no |x_j| / ||A_j||
+ * score); nothing in the library or the package selects it by default.  For column j of a matrix with a CSC
+ * layout, with entries a_k, k in [colptr[j], colptr[j+1]) in stored order (duplicates and unsorted inner indices
+ * are walked as stored):
+ *     q_j     = (((+0.0 + a_k0*a_k0) + a_k1*a_k1) + ...)   every product and every sum rounded separately
+ *     norm_j  = sqrt(q_j)                                  correctly rounded (== np.sqrt)
+ *     num_j   = |x_j|                                      numerator SX_NORM_ABS
+ *     num_j   = min(x_j - l_j, u_j - x_j), and |x_j| where l_j = -inf and u_j = +inf
+ *                                                          numerator SX_NORM_GAP; np.minimum: NaN propagates
+ *     score_j = (q_j == 0) ? +0.0 : num_j / norm_j         IEEE division; an empty or all-zero column scores +0.0
+ * Nothing is clamped: q_j = inf gives a score of +-0, a negative gap a negative score, NaN propagates.
+ * sx_column_norms_dev: sumsq (q) and norm have n entries, either may be NULL.
+ * sx_score_norm_dev: x, l, u, score have n entries; l and u may be NULL for SX_NORM_ABS.  norm_in == NULL: the
+ *   norms are computed in the same launch (one walk over the values; the inner indices are not read).  With
+ *   norm_in (n entries, from sx_column_norms_dev) the call is elementwise -- score_j = (norm_in_j == 0) ? +0.0 :
+ *   num_j / norm_in_j -- and its results are bit-identical to the fused call's.
+ * Full matrices and CSC shards (sx_matrix_create_single, is_csc != 0) are accepted; a row shard gets
+ * SX_ERR_INVALID.  n == 0 returns SX_OK. */
+#define SX_NORM_ABS 0
+#define SX_NORM_GAP 1
+int sx_column_norms_dev(sx_ctx *ctx, const sx_matrix *A, double *sumsq, double *norm);
+int sx_score_norm_dev(sx_ctx *ctx, const sx_matrix *A, const double *x, const double *l, const double *u,
+                      int numerator, const double *norm_in, double *score);
+int sx_score_norm(sx_ctx *ctx, const sx_matrix *A, const double *x, const double *l, const double *u,
+                  int numerator, const double *norm_in, double *score);
+
 /* ------------------------------------------------------------------ K10 on the OT structure
  * replaces get_reduced_cost_for_original_OT + the reduced-cost test (network_methods/net_manager.py:
  * 483,496) without materialising the kron incidence matrix of formats.py:156-159:

@@ -195,6 +195,12 @@ class HipOps:
         self.ctx.score_columns(A, self._w(y), self._w(c), None, None, None, 0.0, self._w(s_d), None)
         return s_d
 
+    def norm_score(self, A, x, l, u, numerator):
+        """The optional norm-scaled indicator of the own column block (sx_score_norm_dev; the norms stay cached on A)."""
+        score = self.empty(A.shape[1], np.float64)
+        self.ctx.score_norm(A, self._w(x), self._w(l), self._w(u), numerator, norm=A.column_norms(), score=self._w(score))
+        return score
+
     def fixed_rhs(self, A_rows, code_all, u_all, l_all, b_loc, out):
         self.ctx.fixed_rhs(A_rows, self._w(code_all), self._w(u_all), self._w(l_all), self._w(b_loc), self._w(out))
 
@@ -293,6 +299,34 @@ def _ops_default(dist):
     return HipOps(Context(dev, stream.cuda_stream), torch)
 
 
+def _merge_top_k(sharded, key_loc, block: Block, k: int) -> np.ndarray:
+    """Global indices of the k largest keys over all ranks, ranked by the library's rule (K9: descending key, ties
+    by descending index, NaN first): every rank ranks the keys of its own block (``ops.top_k``), the W candidate
+    lists of length <= k are all-gathered and merged on the host.  Shared by ``ShardedMCF.top_arcs`` and
+    ``ShardedLP.top_columns``; ``sharded`` supplies ``ops``, ``dist`` and ``ex``."""
+    import torch
+    o = sharded.ops
+    kk = min(int(k), block.size)
+    keys, idx = o.top_k(key_loc, kk)
+    rec = np.zeros((int(k), 2), dtype=np.float64)
+    rec[:, 1] = -1.0                                                 # padding up to k records: no index
+    rec[:kk, 0] = keys
+    rec[:kk, 1] = (idx + block.start).astype(np.float64)             # indices are exact in a double (< 2^53)
+    t = torch.from_numpy(rec.reshape(-1))
+    if sharded.dist is not None:
+        t = t.to(getattr(o, "device", "cpu"))
+        parts = [torch.empty_like(t) for _ in range(sharded.ex.world)]
+        sharded.dist.all_gather(parts, t)
+        allrec = np.concatenate([p.cpu().numpy().reshape(-1, 2) for p in parts])
+    else:
+        allrec = rec
+    allrec = allrec[allrec[:, 1] >= 0]
+    nan = np.isnan(allrec[:, 0])
+    # NaN first, then key descending, then index descending
+    order = np.lexsort((-allrec[:, 1], np.where(nan, 0.0, -allrec[:, 0]), ~nan))
+    return allrec[order[:int(k)], 1].astype(np.int64)
+
+
 class ShardedLP:
     """One rank's share of a GeneralLP ``min c^T x, A x (=|<) b, l <= x <= u``: a column block of A (both layouts;
     K1 scoring, K10 pricing, the CG's two products, compaction) and a row block (row layout; K2 scoring, the
@@ -344,6 +378,21 @@ class ShardedLP:
                               dtype=torch.int64, device=getattr(o, "device", "cpu"))
         counts = self.ex.sum_counts(counts)
         return self.code_loc, self.flag_loc, [int(t) for t in counts.cpu()]
+
+    # ---- optional norm-scaled indicator (no reference counterpart; never selected by default) --------
+    def norm_indicator(self, x: np.ndarray, numerator: str = "gap"):
+        """|x_j| (``"abs"``) or the distance to the nearer bound (``"gap"``) over ||A_j|| for the own column block:
+        a column's norm needs its own entries only, so there is no communication and the bits are the
+        single-device call's."""
+        o = self.ops
+        x_loc = o.vec(np.asarray(x, dtype=np.float64)[self.cols.start:self.cols.stop])
+        self.norm_ind_loc = o.norm_score(self.A_cols, x_loc, self.l_loc, self.u_loc, numerator)
+        return self.norm_ind_loc
+
+    def top_columns(self, k: int) -> np.ndarray:
+        """Global indices of the k columns with the largest ``norm_indicator`` (call that first), ranked as the
+        single-device ranking ranks them: per-rank candidate lists, one all-gather, merged on the host."""
+        return _merge_top_k(self, self.norm_ind_loc, self.cols, k)
 
     def price(self, y: np.ndarray, vbasis_loc: Optional[np.ndarray] = None, tol: float = 1e-6):
         """Global pricing result (min reduced cost, its global column, violations): one 24-byte all-gather."""
@@ -733,22 +782,4 @@ class ShardedMCF:
         (descending indicator, ties by descending arc index): each rank ranks its own arcs, the W candidate lists
         of length <= k are all-gathered and merged -- only queue *prefixes* are ever consumed
         (network_methods/algorithms.py:114-115), so no global sort is needed."""
-        import torch
-        o = self.ops
-        kk = min(int(k), self.arcs.size)
-        keys, idx = o.top_k(self.ind_loc, kk)
-        rec = np.zeros((int(k), 2), dtype=np.float64)
-        rec[:, 0] = -np.inf
-        rec[:kk, 0] = keys
-        rec[:kk, 1] = (idx + self.arcs.start).astype(np.float64)       # arc indices are exact in a double (< 2^53)
-        t = torch.from_numpy(rec.reshape(-1))
-        if self.dist is not None:
-            t = t.to(getattr(o, "device", "cpu"))
-            parts = [torch.empty_like(t) for _ in range(self.ex.world)]
-            self.dist.all_gather(parts, t)
-            allrec = np.concatenate([p.cpu().numpy().reshape(-1, 2) for p in parts])
-        else:
-            allrec = rec
-        allrec = allrec[allrec[:, 0] > -np.inf]
-        order = np.lexsort((-allrec[:, 1], -allrec[:, 0]))               # key descending, then index descending
-        return allrec[order[:int(k)], 1].astype(np.int64)
+        return _merge_top_k(self, self.ind_loc, self.arcs, k)

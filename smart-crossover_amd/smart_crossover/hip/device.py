@@ -29,6 +29,16 @@ def _ptr(a) -> Optional[int]:
     raise TypeError(f"expected DeviceArray, ndarray or None, got {type(a)!r}")
 
 
+def _norm_numerator(numerator) -> int:
+    """"abs" / "gap" (or the SX_NORM_* value itself) -> SX_NORM_ABS / SX_NORM_GAP."""
+    if isinstance(numerator, str):
+        try:
+            return {"abs": _l.NORM_ABS, "gap": _l.NORM_GAP}[numerator]
+        except KeyError:
+            raise ValueError(f"numerator must be 'abs' or 'gap', got {numerator!r}") from None
+    return int(numerator)
+
+
 class Context:
     """One HIP device + stream + scratch space (``sx_ctx``)."""
 
@@ -214,6 +224,20 @@ class Context:
             out = self.empty(key.size, np.int64)
         _l.check(self._lib.sx_argsort_desc_dev(self.handle, key.size, key.ptr, out.ptr))
         return out
+
+    def column_norms(self, A, sumsq=None, norm=None) -> None:
+        """Sum of squares and 2-norm of every column of A, entries in stored order (sx_column_norms_dev)."""
+        _l.check_sx(self._lib.sx_column_norms_dev(self.handle, A.handle, _ptr(sumsq), _ptr(norm)))
+
+    def score_norm(self, A, x, l, u, numerator, norm=None, score=None) -> "DeviceArray":
+        """The optional norm-scaled column indicator (sx_score_norm_dev): ``numerator`` is "abs" (|x_j|) or "gap"
+        (distance to the nearer bound, |x_j| for free columns) over ||A_j||.  With ``norm`` (from ``column_norms``) the
+        call is elementwise; without, the norms are computed in the same launch.  Same bits either way."""
+        if score is None:
+            score = self.empty(A.shape[1], np.float64)
+        _l.check_sx(self._lib.sx_score_norm_dev(self.handle, A.handle, _ptr(x), _ptr(l), _ptr(u),
+                                                _norm_numerator(numerator), _ptr(norm), _ptr(score)))
+        return score
 
     def price_ot(self, S, D, M, y, tol=1e-6, rc=None, result: Optional["DeviceArray"] = None):
         if result is None:
@@ -535,7 +559,21 @@ class DeviceMatrix:
             out.update(st=st, chunks=ch, rowstart=rs.reshape(ncells, stride), idx=idx, val=val)
         return out
 
+    def column_norms(self) -> "DeviceArray":
+        """||A_j|| of every column as a device array (``Context.column_norms``), computed on the first call and
+        kept on the matrix: the norms depend on A only, so every later indicator call is elementwise."""
+        norms = getattr(self, "_col_norms", None)
+        if norms is None:
+            norms = self.ctx.empty(self.shape[1], np.float64)
+            self.ctx.column_norms(self, norm=norms)
+            self._col_norms = norms
+        return norms
+
     def free(self) -> None:
+        norms = getattr(self, "_col_norms", None)
+        if norms is not None:
+            norms.free()
+            self._col_norms = None
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
             self.ctx._lib.sx_matrix_destroy(self.handle)
         self.handle = None

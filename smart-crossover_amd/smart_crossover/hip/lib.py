@@ -19,6 +19,10 @@ SX_ERR_UNSUPPORTED = -4
 CODE_LOW = 1
 CODE_UP = 2
 
+# numerators of the norm-scaled column indicator (sx_score_norm)
+NORM_ABS = 0
+NORM_GAP = 1
+
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 DEFAULT_LIB = os.path.join(_PKG_ROOT, "lib", "libsxhip.so")
 
@@ -29,6 +33,11 @@ class SxLibraryError(RuntimeError):
 
 class SxError(RuntimeError):
     """A libsxhip call failed with SX_ERR_HIP."""
+
+
+class SxInvalidError(SxError, ValueError):
+    """SX_ERR_INVALID from an entry point whose Python method promises an SxError (the norm-scaled
+    indicator on a matrix without a CSC layout); still a ValueError, as every SX_ERR_INVALID is."""
 
 
 class PriceResult(C.Structure):
@@ -112,6 +121,9 @@ PROTOTYPES = {
     "sx_flow_indicator_ot_dev": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "sx_spanning_tree_ot_dev": (_int, [_vp, _i64, _i64, _vp, _vp]),
     "sx_argsort_desc_dev": (_int, [_vp, _i64, _vp, _vp]),
+    "sx_column_norms_dev": (_int, [_vp, _vp, _vp, _vp]),
+    "sx_score_norm_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
+    "sx_score_norm": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
     "sx_price_ot_dev": (_int, [_vp, _i64, _i64, _vp, _vp, _dbl, _vp, _vp]),
     "sx_projector_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _int, _vp, _vp, C.POINTER(CgResult)]),
     "sx_projector_std_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _int, _vp, _vp, C.POINTER(CgResult)]),
@@ -212,6 +224,14 @@ def check(rc: int) -> None:
     if rc == SX_ERR_UNSUPPORTED:
         raise NotImplementedError(msg)
     raise SxError(msg)
+
+
+def check_sx(rc: int) -> None:
+    """``check`` whose SX_ERR_INVALID is an SxError as well as a ValueError."""
+    try:
+        check(rc)
+    except ValueError as exc:
+        raise SxInvalidError(str(exc)) from None
 
 
 def device_count() -> int:

@@ -11,6 +11,8 @@ Everything between the solver calls runs on the MI355X through libsxhip.so:
     K3  perturbed cost      c + min(xi/x_real*sf/1e-2, 1e6)        sx_x_real_dev, sx_perturb_cost_dev
     K4  projector           ||(I - Y^T (YY^T)^+ Y) X c||, matrix-free CG   sx_projector_dev
     K6  sub-problem         A[:, non_fix], right-hand side, gathers   (LPManager.update_subproblem)
+    K17 norm indicator      gap_j / ||A_j||, ranked by K9 -- an extra the reference does not have, opt-in only
+                                                                   sx_score_norm_dev (get_norm_indicator)
 
 The LP re-solves go through the ``SolverCaller`` seam exactly as in the reference (``solver=``).
 Printed messages are the reference's (its log scrapers key on them).
@@ -231,6 +233,34 @@ def get_x_perturb_val(lp: GeneralLP, x: np.ndarray) -> np.ndarray:
     out = dv.ctx.empty(dv.n, np.float64)
     dv.ctx.x_real(dv.n, dv.x, dv.l, dv.u, out, False)
     return out.download()
+
+
+def _norm_indicator_device(lp: GeneralLP, x: np.ndarray, numerator: str):
+    """(context, device vector) of the norm-scaled indicator; the column norms stay cached on the resident matrix."""
+    from smart_crossover.hip.resident import resident_for
+    res = resident_for(lp)
+    gap = numerator != "abs"
+    score = res.ctx.score_norm(res.A, res.put(x), res.put(lp.l) if gap else None, res.put(lp.u) if gap else None,
+                               numerator, norm=res.A.column_norms())
+    return res.ctx, score
+
+
+def get_norm_indicator(lp: GeneralLP, x: np.ndarray, numerator: str = "gap") -> np.ndarray:
+    """Optional column indicator that does not depend on the column scaling of the LP: the distance of x_j to its
+    nearer bound (``numerator="gap"``; |x_j| for free columns) or |x_j| (``"abs"``) over ||A_j||_2, +0.0 for an empty
+    column (include/sxhip.h, K17).  An extra without a counterpart in the reference: nothing selects it by default."""
+    _, score = _norm_indicator_device(lp, x, numerator)
+    return score.download()
+
+
+def rank_by_norm_indicator(lp: GeneralLP, x: np.ndarray, k: Optional[int] = None, numerator: str = "gap") -> np.ndarray:
+    """Column indices by descending ``get_norm_indicator``, ranked on the device (K9: equal keys by descending
+    index, NaN first); the first ``k`` of them when ``k`` is given."""
+    ctx, score = _norm_indicator_device(lp, x, numerator)
+    if score.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    order = ctx.argsort_desc(score)
+    return order.download() if k is None else order.download(min(int(k), order.size))
 
 
 def _assemble_std(lp: GeneralLP, proj_cols, proj_rows) -> np.ndarray:
