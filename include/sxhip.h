@@ -67,9 +67,11 @@ int sx_ctx_sync(sx_ctx *ctx);
  * with nt / sc1 / sc0 sc1 / nt sc1), "chunk" 2048/4096 (default 4096), "window" (LDS operand window of the
  * column walk in K1/K10: -1 auto [default: decided per matrix from its index clustering on first use],
  * 0 off, 1/2/4/8 tiles per window load), "graph" 0/1 (default 1: hipGraph replay of the CG iteration batch),
- * "rb_stage_long" (0/1, default 0: in the column-blocked row layout the products of the long rows come from a
- * column-ordered pre-pass instead of one gathered 128-byte line per entry -- bit-identical, measured slower, kept
- * as an experiment; read when a layout is built),
+ * "rb_stage_long" (in the column-blocked row layout the products of the long rows -- the linking rows of an LP -- come
+ * from a column-ordered pre-pass, which sorts them in LDS into the layout's order and writes them in whole lines, instead
+ * of one gathered 128-byte line of x per entry: -1 auto [default: layouts with at least 2^21 long entries], 0 never,
+ * 1 whenever there are long rows; bit-identical either way, about 26 bytes of device memory per long entry; read when
+ * a layout is built),
  * "slabs" (operand slabs of a walk whose gathers have no locality, csrc/sx_slabs.h -- K1, K2, K10: -1 auto [default:
  * operand beyond 3.6 MB, one slab per 3.2 MB, at least 4M entries, carries no heavier than 1.25 x the entry stream; the
  * LDS window and the column-blocked rows are asked first], 0 never, 2..256 that many slabs; bit-identical either way --
@@ -162,6 +164,13 @@ int sx_matrix_download_csr(const sx_matrix *A, int64_t *rowptr, int32_t *col, do
 int sx_matrix_rowblock_info(sx_ctx *ctx, const sx_matrix *A, int64_t *info);
 int sx_matrix_rowblock_download(sx_ctx *ctx, const sx_matrix *A, void *st, void *chunks, uint16_t *rowstart,
                                 int32_t *idx, double *val);
+/* Side arrays of the layout's staged long rows (option "rb_stage_long"; csrc/sx_rowblock.h): info[0..2] = long
+ * entries nl (<= 0: the long rows are gathered in the walk and there is nothing to download), long slots nls, entries
+ * per piece of the pre-pass.  The second call copies lcol / lval / lperm [nl] and lsrc [nls + 8] to the host
+ * (NULL = skip) -- for tests and tools. */
+int sx_matrix_rowblock_long_info(sx_ctx *ctx, const sx_matrix *A, int64_t *info);
+int sx_matrix_rowblock_long_download(sx_ctx *ctx, const sx_matrix *A, int32_t *lcol, double *lval, uint16_t *lperm,
+                                     int32_t *lsrc);
 /* Operand slabs of A's row walk (which = 0) or column walk (which = 1) under the context's "slabs" option (built now
  * if they are due; csrc/sx_slabs.h): info[0..2] = slabs, operand indices per slab, segments; all zero when the walk
  * is the plain one.  For tests, tools and bench.py; the walks (sx_score_columns_dev / sx_score_rows_dev /

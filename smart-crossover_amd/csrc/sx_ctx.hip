@@ -210,7 +210,8 @@ SX_API int sx_ctx_set_option(sx_ctx *ctx, const char *key, int64_t value) {
         SX_REQUIRE(value >= 1 && value <= 64, "rb_long_rows must be in [1, 64]");
         ctx->opt_rb_long_rows = static_cast<int>(value); // (read when a layout is built)
     } else if (!strcmp(key, "rb_stage_long")) {
-        ctx->opt_rb_stage_long = value ? 1 : 0; // (read when a layout is built)
+        SX_REQUIRE(value >= -1 && value <= 1, "rb_stage_long must be -1 (auto), 0 (never) or 1 (whenever there are long rows)");
+        ctx->opt_rb_stage_long = static_cast<int>(value); // (read when a layout is built)
     } else if (!strcmp(key, "spx_check")) {
         SX_REQUIRE(value >= 64 && value % 64 == 0, "spx_check must be a positive multiple of 64 pivots");
         ctx->opt_spx_check = static_cast<int>(value);

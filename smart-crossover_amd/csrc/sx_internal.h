@@ -112,9 +112,9 @@ struct sx_ctx {
     int opt_rb_dense_min = 512; // entries from which a column block of a super-tile gets an LDS window (read when a layout is built;
                                 // sx_rowblock.h RB_DENSE_MIN)
     int opt_rb_long_rows = 64; // rows per super-tile of long rows (read when a layout is built; sx_rowblock.h RB_LONG_ROWS)
-    int opt_rb_stage_long = 0; // row-blocked layout: products of the long rows by a column-ordered pre-pass (0: gather in the
-                               // walk).  Measured SLOWER (K2 0.442 vs 0.381 ms at config 5: the 1e7 scattered 8-byte stores cost more
-                               // than the 1e7 gathered lines they replace; profiles/r03/experiments/k2_long_row_staging.md): off
+    int opt_rb_stage_long = -1; // row-blocked layout: products of the long rows by a column-ordered pre-pass that writes them
+                                // piece by piece in the layout's order (sx_rowblock.h; read when a layout is built): -1 from
+                                // RB_STAGE_AUTO_NL long entries on, 0 never (gather in the walk), 1 whenever there are long rows
 };
 
 // Device memory of the library (sx_pool.hip): hipMalloc / hipFree with freed blocks kept for the next request of their size

@@ -41,7 +41,8 @@ struct sx_rb_chunk {
     int32_t cell;  // cell number (-> rowstart)
     int32_t base;  // offset of the chunk's first entry inside its cell
     int32_t fresh; // 1: first chunk of its cell (new rowstart, new window)
-    int32_t staged; // 1: chunk of a long-row super-tile whose products a pre-pass leaves in lprod (below)
+    int32_t staged; // > 0: chunk of a long-row super-tile whose products a pre-pass leaves in lprod (below);
+                    // staged - 1 = long slot of the chunk's first entry (-> lsrc)
 };
 
 struct sx_rb_supertile {
@@ -67,6 +68,9 @@ constexpr int RB_LONG_ROWS = 64;       // rows per super-tile of long rows
 constexpr int RB_LONG_BUDGET = 65536;  // entries per super-tile of long rows
 constexpr int RB_RS_STRIDE = RB_R + 4; // uint16 slots per cell in rowstart[]
 constexpr int RB_CELL_MAX = 65535;
+constexpr int RB_PIECE = 8192;         // long entries per piece of the product pre-pass: 8 bytes each in LDS, 64 KiB
+                                       // (4096 / 16384 measured slower: profiles/r05/k2_long_pieces.md); ranks are uint16
+constexpr int64_t RB_STAGE_AUTO_NL = 1 << 21; // "rb_stage_long" -1: staged from this many long entries on
 
 struct sx_rowblock {
     int64_t nst = 0, ncells = 0, nchunks = 0, nent = 0; // nent: entries incl. gaps (idx / val hold nent + 8)
@@ -77,13 +81,19 @@ struct sx_rowblock {
     int32_t *idx = nullptr;
     double *val = nullptr;
     // Long rows (the linking rows of an LP) gather x one 128-byte line per entry -- 1.28 GB of the 2.26 GB K2 moved at
-    // config 5.  Their entries are therefore ALSO kept sorted by column (lcol / lval, and le = the entry's slot in
-    // idx / val): a pre-pass streams that list and x in column order, forms the same rounded products and scatters
-    // them to lprod[le]; the walk then reads the products of a staged chunk instead of entries + gathers.  Same
-    // products, same order of the adds: bit-identical sums.
-    int64_t nl = 0;
-    int32_t *lcol = nullptr, *le = nullptr;
-    double *lval = nullptr, *lprod = nullptr;
+    // config 5.  In the staged mode (option "rb_stage_long") their entries are therefore ALSO kept sorted by
+    // (column, slot) -- lcol / lval -- and cut into pieces of RB_PIECE consecutive list entries.  A pre-pass, one
+    // workgroup per piece, streams the list and x in column order, forms the same rounded products, sorts them in LDS
+    // into the layout's own order (lperm[i] = rank of list entry i among the slots of its piece) and writes the piece
+    // to lprod in whole lines.  The slots of the long super-tiles, one super-tile after the other, are the "long
+    // slots" 0 .. nls - 1; lsrc[long slot] = piece base + rank says where the product of that slot lies (0 for the
+    // gap behind a cell), and chunk.staged - 1 is the long slot of a chunk's first entry.  The walk loads lsrc
+    // instead of entries and gathers products that lie in a few contiguous runs per chunk.  Same products, same order
+    // of the adds: bit-identical sums.  tools/rb_layout.py stage_long states the same arrays in numpy.
+    int64_t nl = 0, nls = 0; // long entries (-1: too many for 32-bit slots, gathered) / long slots (lsrc holds nls + 8)
+    int32_t *lcol = nullptr, *lsrc = nullptr;
+    uint16_t *lperm = nullptr;
+    double *lval = nullptr, *lprod = nullptr; // lprod: nl + 8 doubles, piece after piece
     // Optional block -> super-tile map of the walks (option "rb_long_xcd", built on first use; sx_rowblock.hip rb_build_order):
     // the long-row super-tiles dealt over the eight XCDs, the ordinary ones behind them in ascending order.  order[b] < 0: no tile.
     mutable int32_t *order = nullptr;

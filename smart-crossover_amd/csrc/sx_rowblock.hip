@@ -16,6 +16,9 @@
 // neighbouring super-tiles re-read, from the XCD's L2.
 // MI355X, config 5 (1e6 x 1e7, 8e7 entries): 0.36 ms against 0.61 ms for the plain walk
 // (profiles/r02/rb_bench_*.txt), L1<->L2 requests 8.45e7 -> ~2e7.
+// Super-tiles of long rows in the staged mode (sx_rowblock.h) take their products from the pre-pass
+// k_rb_long_products instead (rb_supertile_sum_staged): pre-pass 0.05 ms + walk 0.30 ms against 0.39 ms with the
+// long rows gathered, 2.25 -> 1.54 GB moved (profiles/r05/k2_long_pieces.md).
 #include "sx_internal.h"
 #include "sx_rowblock.h"
 #include "sx_segwalk.h"
@@ -31,6 +34,8 @@ constexpr int RB_NT = 2;                        // cache policy of the entry str
 constexpr int RB_MINW = 6;                      // waves per SIMD the register budget allows (3 workgroups / CU)
 static_assert(RB_CHUNK % (RB_TW * 4) == 0 && RB_CWIN % (RB_TW * 2) == 0, "chunk / window vs workgroup");
 
+typedef int sx_v2i __attribute__((ext_vector_type(2)));
+
 struct RbEntries { // the entries one lane stages of one chunk
     sx_v4i i[RB_NQ];
     sx_v2d v01[RB_NQ], v23[RB_NQ];
@@ -41,18 +46,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rb_rsrc(const void *p, uint32_
 }
 
 __device__ __forceinline__ void rb_load(RbEntries &E, const sx_rb_chunk &c, const int32_t *__restrict__ idx,
-                                        const double *__restrict__ val, const double *__restrict__ lprod) {
+                                        const double *__restrict__ val) {
     const uint32_t ne4 = static_cast<uint32_t>((c.ne + 3) & ~3);
-    if (c.staged && lprod) { // the chunk's products are there already: 8 bytes per entry, no gather
-        const __amdgpu_buffer_rsrc_t rp = rb_rsrc(lprod + c.e0, ne4 * 8u);
-        const int tid = threadIdx.x;
-#pragma unroll
-        for (int q = 0; q < RB_NQ; ++q) {
-            E.v01[q] = __builtin_bit_cast(sx_v2d, __builtin_amdgcn_raw_buffer_load_b128(rp, tid * 32, q * RB_TW * 32, RB_NT));
-            E.v23[q] = __builtin_bit_cast(sx_v2d, __builtin_amdgcn_raw_buffer_load_b128(rp, tid * 32 + 16, q * RB_TW * 32, RB_NT));
-        }
-        return;
-    }
     const __amdgpu_buffer_rsrc_t ri = rb_rsrc(idx + c.e0, ne4 * 4u), rv = rb_rsrc(val + c.e0, ne4 * 8u);
     const int tid = threadIdx.x;
 #pragma unroll
@@ -65,17 +60,9 @@ __device__ __forceinline__ void rb_load(RbEntries &E, const sx_rb_chunk &c, cons
 
 // lanes past the chunk hold zeros (index 0, value 0.0): their products land in slots no row segment covers
 __device__ __forceinline__ void rb_stage(const RbEntries &E, const sx_rb_chunk &c, const double *win,
-                                         const double *__restrict__ x, double *prod, bool staged) {
+                                         const double *__restrict__ x, double *prod) {
     const int tid = threadIdx.x;
-    if (staged) {
-#pragma unroll
-        for (int q = 0; q < RB_NQ; ++q) {
-            const int off = q * RB_TW * 4 + tid * 4;
-            double2 *dst = reinterpret_cast<double2 *>(prod + off);
-            dst[0] = make_double2(E.v01[q].x, E.v01[q].y);
-            dst[1] = make_double2(E.v23[q].x, E.v23[q].y);
-        }
-    } else if (c.col0 != RB_NO_WINDOW) {
+    if (c.col0 != RB_NO_WINDOW) {
         const double *w0 = win - c.col0; // only dereferenced inside [win, win + RB_CWIN)
 #pragma unroll
         for (int q = 0; q < RB_NQ; ++q) {
@@ -171,8 +158,102 @@ struct RbLayout {
     const int32_t *__restrict__ idx;
     const double *__restrict__ val;
     int64_t nst;
-    const double *__restrict__ lprod; // products of the staged (long-row) chunks, or nullptr
+    const double *__restrict__ lprod; // staged (long-row) chunks: products left by the pre-pass, or nullptr
+    const int32_t *__restrict__ lsrc; // ... and where the product of a long slot lies in lprod
 };
+
+// rb_supertile_sum for a super-tile of long rows in the staged mode: every chunk's products lie in lprod already
+// (sx_rowblock.h).  Two loads deep, so that the gather never waits for its addresses: step k loads the lsrc quads of
+// chunk k+2, gathers the products of chunk k+1 (its lsrc quads came in during step k-1), parks the products of chunk k
+// (gathered during step k-1) lane-linear in LDS, and consumes them as every other chunk is consumed.
+// The trade: this is a second copy of the step skeleton of rb_supertile_sum (record table, row starts, barriers) for
+// 1.3 % of K2 over routing staged chunks through the generic step (lsrc one chunk ahead, gather in the stage phase:
+// profiles/r05/k2_long_pieces.md); in return the generic step carries no staged branch.  A change to the table
+// regrouping or to the barriers of one loop belongs in the other as well.
+__device__ __forceinline__ void rb_supertile_sum_staged(const RbLayout &L, const sx_rb_supertile &S, RbLds &lds,
+                                                        double (&acc)[RB_RPL]) {
+    const int tid = threadIdx.x;
+    const int *ck = reinterpret_cast<const int *>(L.chunks + S.chunk0);
+    const int n = S.nchunks;
+    int g = 0;
+    auto load_tab = [&]() {
+        for (int i = tid; i < RB_TABN * 8; i += RB_TW) {
+            int rec = g + i / 8;
+            rec = rec < n ? rec : n - 1;
+            lds.tab[i] = ck[static_cast<int64_t>(rec) * 8 + (i & 7)];
+        }
+    };
+    auto load_rs = [&](int (&rs)[RB_RPL][2], const sx_rb_chunk &c) {
+        const __amdgpu_buffer_rsrc_t rr = rb_rsrc(L.rowstart + static_cast<int64_t>(c.cell) * RB_RS_STRIDE, RB_RS_STRIDE * 2u);
+#pragma unroll
+        for (int r = 0; r < RB_RPL; ++r) {
+            const int row = tid + r * RB_TW;
+            const int k0 = row < S.nrows ? row : S.nrows, k1 = row + 1 < S.nrows ? row + 1 : S.nrows;
+            rs[r][0] = static_cast<uint16_t>(__builtin_amdgcn_raw_buffer_load_b16(rr, k0 * 2, 0, 0));
+            rs[r][1] = static_cast<uint16_t>(__builtin_amdgcn_raw_buffer_load_b16(rr, k1 * 2, 0, 0));
+        }
+    };
+    auto load_src = [&](sx_v4i (&I)[RB_NQ], const sx_rb_chunk &c) { // lanes past the chunk read 0: lprod[0], as a gap does
+        const __amdgpu_buffer_rsrc_t rs = rb_rsrc(L.lsrc + (c.staged - 1), static_cast<uint32_t>((c.ne + 3) & ~3) * 4u);
+#pragma unroll
+        for (int q = 0; q < RB_NQ; ++q) I[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, tid * 16, q * RB_TW * 16, RB_NT);
+    };
+    auto gather = [&](double (&P)[RB_NQ][4], const sx_v4i (&I)[RB_NQ]) {
+#pragma unroll
+        for (int q = 0; q < RB_NQ; ++q) {
+            P[q][0] = L.lprod[I[q].x];
+            P[q][1] = L.lprod[I[q].y];
+            P[q][2] = L.lprod[I[q].z];
+            P[q][3] = L.lprod[I[q].w];
+        }
+    };
+    int rs[RB_RPL][2], rs_next[RB_RPL][2];
+    sx_v4i I[2][RB_NQ];
+    double P[2][RB_NQ][4];
+    __syncthreads(); // the previous super-tile of a grid-stride caller is done with the LDS
+    load_tab();
+    __syncthreads();
+    sx_rb_chunk c = rb_record(lds.tab, 0);
+    load_rs(rs, c);
+    load_src(I[0], c);
+    if (n > 1) load_src(I[1], rb_record(lds.tab, 1));
+    gather(P[0], I[0]);
+    auto step = [&](sx_v4i (&Icur)[RB_NQ], double (&Pcur)[RB_NQ][4], sx_v4i (&Inext)[RB_NQ], double (&Pnext)[RB_NQ][4], int k) {
+        const bool has_next = k + 1 < n;
+        const sx_rb_chunk cn = rb_record(lds.tab, (has_next ? k + 1 : k) - g);
+        const bool open = has_next && cn.fresh;
+        if (open) load_rs(rs_next, cn);
+        if (has_next) gather(Pnext, Inext);
+        if (k + 2 < n) load_src(Icur, rb_record(lds.tab, k + 2 - g)); // (the gather of chunk k has read Icur)
+#pragma unroll
+        for (int q = 0; q < RB_NQ; ++q) {
+            double2 *dst = reinterpret_cast<double2 *>(lds.prod + q * RB_TW * 4 + tid * 4);
+            dst[0] = make_double2(Pcur[q][0], Pcur[q][1]);
+            dst[1] = make_double2(Pcur[q][2], Pcur[q][3]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < RB_RPL; ++r) rb_consume(acc[r], rs[r][0], rs[r][1], c.base, c.ne, lds.prod);
+        if (open) {
+#pragma unroll
+            for (int r = 0; r < RB_RPL; ++r) {
+                rs[r][0] = rs_next[r][0];
+                rs[r][1] = rs_next[r][1];
+            }
+        }
+        if (has_next && k + 1 == g + RB_TAB) { // next group of records
+            __syncthreads();
+            g += RB_TAB;
+            load_tab();
+        }
+        __syncthreads();
+        c = cn;
+    };
+    for (int k = 0; k < n; k += 2) {
+        step(I[0], P[0], I[1], P[1], k);
+        if (k + 1 < n) step(I[1], P[1], I[0], P[0], k + 1);
+    }
+}
 
 // acc[r] = sum of row S.row0 + tid + r * RB_TW over the super-tile (0 for rows beyond its end); all lanes of the
 // workgroup call it
@@ -184,6 +265,10 @@ __device__ __forceinline__ void rb_supertile_sum(const RbLayout &L, const sx_rb_
 #pragma unroll
     for (int r = 0; r < RB_RPL; ++r) acc[r] = 0.0;
     if (n <= 0) return;
+    if (L.lsrc && __builtin_amdgcn_readfirstlane(ck[7]) > 0) { // long rows, staged: all chunks are
+        rb_supertile_sum_staged(L, S, lds, acc);
+        return;
+    }
     int g = 0;
     auto load_tab = [&]() {
         for (int i = tid; i < RB_TABN * 8; i += RB_TW) {
@@ -222,7 +307,7 @@ __device__ __forceinline__ void rb_supertile_sum(const RbLayout &L, const sx_rb_
     sx_rb_chunk c = rb_record(lds.tab, 0);
     load_rs(rs, c);
     if (c.col0 != RB_NO_WINDOW) load_win(wreg, c);
-    rb_load(E[0], c, L.idx, L.val, L.lprod);
+    rb_load(E[0], c, L.idx, L.val);
     if (c.col0 != RB_NO_WINDOW) store_win(wreg);
     __syncthreads();
     auto step = [&](RbEntries &Ecur, RbEntries &Enext, int k) {
@@ -232,8 +317,8 @@ __device__ __forceinline__ void rb_supertile_sum(const RbLayout &L, const sx_rb_
         const bool new_win = open && cn.col0 != RB_NO_WINDOW;
         if (open) load_rs(rs_next, cn);
         if (new_win) load_win(wreg, cn);
-        if (has_next) rb_load(Enext, cn, L.idx, L.val, L.lprod);
-        rb_stage(Ecur, c, lds.win, x, lds.prod, c.staged && L.lprod);
+        if (has_next) rb_load(Enext, cn, L.idx, L.val);
+        rb_stage(Ecur, c, lds.win, x, lds.prod);
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < RB_RPL; ++r) rb_consume(acc[r], rs[r][0], rs[r][1], c.base, c.ne, lds.prod);
@@ -354,47 +439,76 @@ __global__ __launch_bounds__(RB_TW, RB_MINW) void k_rb_cg_a(RbLayout L, int swiz
 }
 
 inline RbLayout layout_of(const sx_rowblock *rb) {
-    return RbLayout{rb->st, rb->chunks, rb->rowstart, rb->idx, rb->val, rb->nst, rb->nl > 0 ? rb->lprod : nullptr};
+    const bool staged = rb->nl > 0;
+    return RbLayout{rb->st, rb->chunks, rb->rowstart, rb->idx, rb->val, rb->nst, staged ? rb->lprod : nullptr, staged ? rb->lsrc : nullptr};
 }
 
-// pre-pass of the long rows: products in column order (x streamed), scattered to their slots.
-// A line of lprod holds 16 consecutive positions of ONE long row, i.e. entries whose columns lie far apart (160,000
-// columns at config 5), so it is completed by many workgroups.  When those sit on different XCDs every L2 writes its
-// part of the line back on its own and the memory side merges them (read-modify-write: measured slower than the
-// gathers it replaces).  Therefore XCD k takes the contiguous k-th eighth of the column-ordered list, tile after tile
-// in dispatch order: the lines a row has open (128 bytes x the number of long rows per XCD) stay in that XCD's L2
-// until they are complete and leave as whole lines.  The three list streams are read once (non-temporal).
-constexpr int RB_LP_TILE = 8 * SX_WG; // entries per workgroup of the pre-pass
-__global__ __launch_bounds__(SX_WG) void k_rb_long_products(int64_t nl, const int32_t *__restrict__ lcol, const double *__restrict__ lval,
-                                                            const int32_t *__restrict__ le, const double *__restrict__ x,
-                                                            double *__restrict__ lprod, const RbCgState *st) {
+// pre-pass of the long rows (staged mode, sx_rowblock.h): one workgroup per piece of RB_PIECE consecutive entries of the
+// column-ordered list.  Phase 1 streams lcol / lval / lperm (read once: non-temporal) and x[lcol] -- ascending columns,
+// nearly coalesced --, forms the rounded products and drops each at its rank in LDS; phase 2 copies the piece to lprod
+// with consecutive 16-byte stores.  No scattered global store: lprod leaves in whole lines (the first pre-pass scattered
+// 8-byte stores, 236 MB written for 80 MB of products: profiles/r03/experiments/k2_long_row_staging.md).
+// XCD k takes the contiguous k-th eighth of the pieces, in dispatch order, so that the x lines neighbouring pieces share
+// stay in one L2.
+constexpr int RB_LP_WG = 1024;                          // lanes per workgroup of the pre-pass
+constexpr int RB_LP_NQ = RB_PIECE / (RB_LP_WG * 4);     // quads of entries per lane
+constexpr int RB_LP_MINW = 8;                           // two workgroups per CU
+static_assert(RB_PIECE % (RB_LP_WG * 4) == 0 && RB_PIECE * 8 <= 65536, "piece vs workgroup / static LDS / uint16 ranks");
+__global__ __launch_bounds__(RB_LP_WG, RB_LP_MINW) void k_rb_long_products(int64_t nl, const int32_t *__restrict__ lcol,
+                                                                           const double *__restrict__ lval,
+                                                                           const uint16_t *__restrict__ lperm,
+                                                                           const double *__restrict__ x, double *__restrict__ lprod,
+                                                                           const RbCgState *st) {
     if (st && st->done) return;
-    const int64_t ntiles = (nl + RB_LP_TILE - 1) / RB_LP_TILE;
-    const int64_t per = (ntiles + 7) >> 3;
-    const int64_t tile = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if ((blockIdx.x >> 3) >= per || tile >= ntiles) return;
-    const int64_t i0 = tile * RB_LP_TILE + threadIdx.x;
-    int32_t c[8], e[8];
-    double v[8];
+    __shared__ double piece_prod[RB_PIECE];
+    const int64_t npieces = (nl + RB_PIECE - 1) / RB_PIECE;
+    const int64_t per = (npieces + 7) >> 3;
+    const int64_t piece = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if ((blockIdx.x >> 3) >= per || piece >= npieces) return;
+    const int64_t i0 = piece * RB_PIECE;
+    const int cnt = static_cast<int>(nl - i0 < RB_PIECE ? nl - i0 : RB_PIECE);
+    const uint32_t cnt4 = static_cast<uint32_t>((cnt + 3) & ~3); // the lists hold 8 zeroed entries behind the last one
+    const __amdgpu_buffer_rsrc_t rc = rb_rsrc(lcol + i0, cnt4 * 4u), rv = rb_rsrc(lval + i0, cnt4 * 8u),
+                                 rp = rb_rsrc(lperm + i0, cnt4 * 2u);
+    const int tid = threadIdx.x;
+    sx_v4i c[RB_LP_NQ];
+    sx_v2d v01[RB_LP_NQ], v23[RB_LP_NQ];
+    sx_v2i pm[RB_LP_NQ];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int64_t i = i0 + q * SX_WG;
-        const bool ok = i < nl;
-        c[q] = ok ? __builtin_nontemporal_load(lcol + i) : 0;
-        e[q] = ok ? __builtin_nontemporal_load(le + i) : -1;
-        v[q] = ok ? __builtin_nontemporal_load(lval + i) : 0.0;
+    for (int q = 0; q < RB_LP_NQ; ++q) { // lanes past the end read zeros: column 0, value 0.0
+        c[q] = __builtin_amdgcn_raw_buffer_load_b128(rc, tid * 16, q * RB_LP_WG * 16, RB_NT);
+        pm[q] = __builtin_amdgcn_raw_buffer_load_b64(rp, tid * 8, q * RB_LP_WG * 8, RB_NT);
+        v01[q] = __builtin_bit_cast(sx_v2d, __builtin_amdgcn_raw_buffer_load_b128(rv, tid * 32, q * RB_LP_WG * 32, RB_NT));
+        v23[q] = __builtin_bit_cast(sx_v2d, __builtin_amdgcn_raw_buffer_load_b128(rv, tid * 32 + 16, q * RB_LP_WG * 32, RB_NT));
     }
-    double xv[8];
+    double xv[RB_LP_NQ][4];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) xv[q] = x[c[q]];
+    for (int q = 0; q < RB_LP_NQ; ++q) {
+        xv[q][0] = x[c[q].x];
+        xv[q][1] = x[c[q].y];
+        xv[q][2] = x[c[q].z];
+        xv[q][3] = x[c[q].w];
+    }
 #pragma unroll
-    for (int q = 0; q < 8; ++q)
-        if (e[q] >= 0) lprod[e[q]] = v[q] * xv[q];
+    for (int q = 0; q < RB_LP_NQ; ++q) {
+        const int off = (q * RB_LP_WG + tid) * 4;
+        const unsigned p01 = static_cast<unsigned>(pm[q].x), p23 = static_cast<unsigned>(pm[q].y);
+        if (off + 0 < cnt) piece_prod[p01 & 0xffffu] = v01[q].x * xv[q][0];
+        if (off + 1 < cnt) piece_prod[p01 >> 16] = v01[q].y * xv[q][1];
+        if (off + 2 < cnt) piece_prod[p23 & 0xffffu] = v23[q].x * xv[q][2];
+        if (off + 3 < cnt) piece_prod[p23 >> 16] = v23[q].y * xv[q][3];
+    }
+    __syncthreads();
+    double *out = lprod + i0; // 16-byte aligned; an odd count writes one double of the padding behind the list
+    for (int k = tid * 2; k < cnt; k += RB_LP_WG * 2)
+        *reinterpret_cast<sx_v2d *>(out + k) = *reinterpret_cast<const sx_v2d *>(piece_prod + k);
 }
 
-inline unsigned rb_lp_grid(int64_t nl) {
-    const int64_t ntiles = (nl + RB_LP_TILE - 1) / RB_LP_TILE;
-    return static_cast<unsigned>(((ntiles + 7) >> 3) << 3);
+inline int rb_long_products(sx_ctx *ctx, const sx_rowblock *rb, const double *x, const RbCgState *st) {
+    const int64_t npieces = (rb->nl + RB_PIECE - 1) / RB_PIECE;
+    hipLaunchKernelGGL(k_rb_long_products, dim3(static_cast<unsigned>(((npieces + 7) >> 3) << 3)), dim3(RB_LP_WG), 0, ctx->stream,
+                       rb->nl, rb->lcol, rb->lval, rb->lperm, x, rb->lprod, st);
+    return SX_OK;
 }
 
 } // namespace
@@ -483,9 +597,7 @@ int sx_rb_score_rows(sx_ctx *ctx, const sx_rowblock *rb, int64_t ncols, const do
     unsigned grid = swz ? static_cast<unsigned>(((rb->nst + 7) >> 3) << 3) : static_cast<unsigned>(rb->nst);
     const int32_t *order = rb_order(ctx, rb);
     if (order) grid = static_cast<unsigned>(rb->order_n);
-    if (rb->nl > 0)
-        hipLaunchKernelGGL(k_rb_long_products, dim3(rb_lp_grid(rb->nl)), dim3(SX_WG), 0, ctx->stream,
-                           rb->nl, rb->lcol, rb->lval, rb->le, x, rb->lprod, static_cast<const RbCgState *>(nullptr));
+    if (rb->nl > 0) SX_TRY(rb_long_products(ctx, rb, x, nullptr));
     hipLaunchKernelGGL(k_rb_score_rows, dim3(grid), dim3(RB_TW), 0, ctx->stream, layout_of(rb), swz, order, x, ncols, b, y,
                        gamma_dual, s_p, flag);
     SX_HIP(hipGetLastError());
@@ -498,9 +610,7 @@ int sx_rb_cg_a(sx_ctx *ctx, const sx_rowblock *rb, int64_t ncols, const void *cg
     const int swz = (ctx->opt_xcd_swizzle && rb->nst >= 64) ? 1 : 0;
     if (swz) g &= ~static_cast<int64_t>(7);
     if (g < 1) g = 1;
-    if (rb->nl > 0)
-        hipLaunchKernelGGL(k_rb_long_products, dim3(rb_lp_grid(rb->nl)), dim3(SX_WG), 0, ctx->stream,
-                           rb->nl, rb->lcol, rb->lval, rb->le, w, rb->lprod, static_cast<const RbCgState *>(cg_state));
+    if (rb->nl > 0) SX_TRY(rb_long_products(ctx, rb, w, static_cast<const RbCgState *>(cg_state)));
     const int32_t *order = swz ? rb_order(ctx, rb) : nullptr;
     hipLaunchKernelGGL(k_rb_cg_a, dim3(static_cast<unsigned>(g)), dim3(RB_TW), 0, ctx->stream, layout_of(rb), swz, order, rb->order_n,
                        static_cast<const RbCgState *>(cg_state), w, ncols, xs, p, q, partial);

@@ -223,44 +223,65 @@ __global__ __launch_bounds__(SX_WG) void k_rb_supertiles(int64_t nst, const int6
     st[s] = r;
 }
 
-// ---- long rows: mark their chunks, list their entries (column, slot), later sorted by column
+// ---- long rows, staged mode (sx_rowblock.h): long slots, the list sorted by (column, slot), pieces
+// one lane per super-tile: width of its slot range if it holds long rows, entries of its chunks
+__global__ __launch_bounds__(SX_WG) void k_rb_long_extent(int64_t nst, const sx_rb_supertile *__restrict__ st,
+                                                          const int32_t *__restrict__ slice, const sx_rb_chunk *__restrict__ chunks,
+                                                          const int64_t *__restrict__ cell_base, const int64_t *__restrict__ cell_e0,
+                                                          int64_t *__restrict__ width, int64_t *__restrict__ chne) {
+    const int64_t s = static_cast<int64_t>(blockIdx.x) * SX_WG + threadIdx.x;
+    if (s >= nst) return;
+    const bool lg = slice[s] != 0;
+    width[s] = lg ? cell_e0[cell_base[s + 1]] - cell_e0[cell_base[s]] : 0;
+    for (int64_t k = st[s].chunk0; k < st[s].chunk0 + st[s].nchunks; ++k) chne[k] = lg ? chunks[k].ne : 0;
+}
 __global__ __launch_bounds__(SX_WG) void k_rb_mark_long(int64_t nst, const sx_rb_supertile *__restrict__ st,
-                                                        const int32_t *__restrict__ slice, sx_rb_chunk *__restrict__ chunks,
-                                                        unsigned long long *__restrict__ count) {
+                                                        const int32_t *__restrict__ slice, const int64_t *__restrict__ cell_base,
+                                                        const int64_t *__restrict__ cell_e0, const int64_t *__restrict__ lbase,
+                                                        sx_rb_chunk *__restrict__ chunks) {
     const int64_t s = static_cast<int64_t>(blockIdx.x) * SX_WG + threadIdx.x;
     if (s >= nst || slice[s] == 0) return;
-    unsigned long long tot = 0;
-    for (int64_t k = st[s].chunk0; k < st[s].chunk0 + st[s].nchunks; ++k) {
-        chunks[k].staged = 1;
-        tot += static_cast<unsigned long long>(chunks[k].ne);
-    }
-    atomicAdd(count, tot);
+    const int64_t lo = cell_e0[cell_base[s]];
+    for (int64_t k = st[s].chunk0; k < st[s].chunk0 + st[s].nchunks; ++k)
+        chunks[k].staged = static_cast<int32_t>(1 + lbase[s] + (chunks[k].e0 - lo));
 }
-// one workgroup per chunk; the order of the list does not matter (it is sorted by column afterwards, and equal
-// columns scatter to different slots)
+// one workgroup per chunk: the list in ascending slot order (the stable sort by column keeps it among equal columns)
 __global__ __launch_bounds__(SX_WG) void k_rb_long_fill(int64_t nchunks, const sx_rb_chunk *__restrict__ chunks,
-                                                        const int32_t *__restrict__ idx, unsigned long long *__restrict__ cursor,
-                                                        uint64_t *__restrict__ key, int32_t *__restrict__ pay) {
-    __shared__ unsigned long long base;
+                                                        const int32_t *__restrict__ idx, const int64_t *__restrict__ chbase,
+                                                        uint64_t *__restrict__ key, int32_t *__restrict__ pay,
+                                                        int32_t *__restrict__ lslot) {
     const int64_t k = blockIdx.x;
     if (k >= nchunks) return;
     const sx_rb_chunk c = chunks[k];
-    if (!c.staged) return;
-    if (threadIdx.x == 0) base = atomicAdd(cursor, static_cast<unsigned long long>(c.ne));
-    __syncthreads();
+    if (c.staged <= 0) return;
+    const int64_t base = chbase[k];
+    const int32_t l0 = c.staged - 1;
     for (int t = threadIdx.x; t < c.ne; t += SX_WG) {
         key[base + t] = static_cast<uint64_t>(static_cast<uint32_t>(idx[c.e0 + t]));
-        pay[base + t] = static_cast<int32_t>(c.e0 + t);
+        pay[base + t] = l0 + t;
+        lslot[l0 + t] = static_cast<int32_t>(c.e0 + t);
     }
 }
+// sorted by column: the lists, and the keys of the second sort (piece, long slot) with the list position as payload
 __global__ __launch_bounds__(SX_WG) void k_rb_long_lists(int64_t nl, const uint64_t *__restrict__ key, const int32_t *__restrict__ pay,
-                                                         const double *__restrict__ val, int32_t *__restrict__ lcol,
-                                                         int32_t *__restrict__ le, double *__restrict__ lval) {
+                                                         const int32_t *__restrict__ lslot, const double *__restrict__ val,
+                                                         int sbits, int32_t *__restrict__ lcol, double *__restrict__ lval,
+                                                         uint64_t *__restrict__ key2, int32_t *__restrict__ pay2) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * SX_WG + threadIdx.x;
     if (i >= nl) return;
+    const int32_t ls = pay[i];
     lcol[i] = static_cast<int32_t>(key[i]);
-    le[i] = pay[i];
-    lval[i] = val[pay[i]];
+    lval[i] = val[lslot[ls]];
+    key2[i] = (static_cast<uint64_t>(i / RB_PIECE) << sbits) | static_cast<uint32_t>(ls);
+    pay2[i] = static_cast<int32_t>(i);
+}
+// sorted by (piece, long slot): position p = piece base + rank
+__global__ __launch_bounds__(SX_WG) void k_rb_long_perm(int64_t nl, const uint64_t *__restrict__ key2, const int32_t *__restrict__ pay2,
+                                                        int sbits, uint16_t *__restrict__ lperm, int32_t *__restrict__ lsrc) {
+    const int64_t p = static_cast<int64_t>(blockIdx.x) * SX_WG + threadIdx.x;
+    if (p >= nl) return;
+    lperm[pay2[p]] = static_cast<uint16_t>(p % RB_PIECE);
+    lsrc[key2[p] & ((static_cast<uint64_t>(1) << sbits) - 1)] = static_cast<int32_t>(p);
 }
 
 // temporaries of one build: freed on every exit path
@@ -319,9 +340,11 @@ int build(sx_ctx *ctx, const sx_matrix *A, bool force, sx_rowblock **out) {
     const int64_t nst = static_cast<int64_t>(cuts.size()) - 1;
     std::vector<int32_t> slice(static_cast<size_t>(nst), 0);
     int64_t nblk = (n + RB_CWIN - 1) / RB_CWIN;
+    int64_t long_entries = 0; // entries of the long-row super-tiles
     for (int64_t k = 0; k < nst; ++k) {
         const int64_t r0 = cuts[static_cast<size_t>(k)], r1 = cuts[static_cast<size_t>(k) + 1];
         if (rowptr[r0 + 1] - rowptr[r0] > RB_LONG_ROW) {
+            long_entries += rowptr[r1] - rowptr[r0];
             const int64_t sl = std::max<int64_t>(1, RB_CHUNK / (r1 - r0));
             slice[static_cast<size_t>(k)] = static_cast<int32_t>(sl);
             int64_t longest = 0;
@@ -440,42 +463,68 @@ int build(sx_ctx *ctx, const sx_matrix *A, bool force, sx_rowblock **out) {
                        d_ch_first, rb->chunks);
     hipLaunchKernelGGL(k_rb_supertiles, dim3(grid1d(nst)), dim3(SX_WG), 0, s, nst, d_cuts, d_cell_base, d_ch_first, rb->st);
     SX_HIP(hipGetLastError());
-    // ---- long rows: their entries once more, sorted by column, for the product pre-pass (sx_rowblock.h)
-    if (ctx->opt_rb_stage_long) {
-        unsigned long long *d_cnt2;
-        SX_TRY(tmp.get(2, &d_cnt2, true, s));
-        hipLaunchKernelGGL(k_rb_mark_long, dim3(grid1d(nst)), dim3(SX_WG), 0, s, nst, rb->st, d_slice, rb->chunks, d_cnt2);
-        unsigned long long nl = 0;
-        SX_HIP(hipMemcpyAsync(&nl, d_cnt2, sizeof(nl), hipMemcpyDeviceToHost, s));
+    // ---- long rows, staged mode: their entries once more, sorted by column and cut into pieces (sx_rowblock.h).
+    // The host knows from the row pointers whether the rule asks for it: a layout that stays gathered pays nothing here.
+    if (long_entries > 0 && (ctx->opt_rb_stage_long > 0 || (ctx->opt_rb_stage_long < 0 && long_entries >= RB_STAGE_AUTO_NL))) {
+        int64_t *d_width, *d_lbase, *d_chne, *d_chbase;
+        SX_TRY(tmp.get(static_cast<size_t>(nst) + 1, &d_width, false, s));
+        SX_TRY(tmp.get(static_cast<size_t>(nst) + 1, &d_lbase, false, s));
+        SX_TRY(tmp.get(static_cast<size_t>(nchunks) + 1, &d_chne, true, s));
+        SX_TRY(tmp.get(static_cast<size_t>(nchunks) + 1, &d_chbase, false, s));
+        hipLaunchKernelGGL(k_rb_long_extent, dim3(grid1d(nst)), dim3(SX_WG), 0, s, nst, rb->st, d_slice, rb->chunks, d_cell_base,
+                           d_cell_e0, d_width, d_chne);
+        SX_TRY(sx_scan_exclusive(ctx, d_width, nst, d_lbase));
+        SX_TRY(sx_scan_exclusive(ctx, d_chne, nchunks, d_chbase));
+        int64_t nl = 0, nls = 0;
+        SX_HIP(hipMemcpyAsync(&nl, d_chbase + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        SX_HIP(hipMemcpyAsync(&nls, d_lbase + nst, sizeof(int64_t), hipMemcpyDeviceToHost, s));
         SX_HIP(hipStreamSynchronize(s));
-        if (nl > 0 && nl < INT32_MAX && nent + 8 < INT32_MAX) {
+        if (nl > 0 && nl < INT32_MAX && nls + 8 < INT32_MAX && nent + 8 < INT32_MAX) {
             uint64_t *lkey[2];
-            int32_t *lpay[2];
+            int32_t *lpay[2], *d_lslot;
             int64_t *lhist, *loffs;
-            const int64_t lblocks = sx_sort_blocks(static_cast<int64_t>(nl));
+            const int64_t lblocks = sx_sort_blocks(nl);
             for (int k = 0; k < 2; ++k) {
                 SX_TRY(tmp.get(static_cast<size_t>(nl), &lkey[k], false, s));
                 SX_TRY(tmp.get(static_cast<size_t>(nl), &lpay[k], false, s));
             }
             SX_TRY(tmp.get(static_cast<size_t>(256 * lblocks + 1), &lhist, false, s));
             SX_TRY(tmp.get(static_cast<size_t>(256 * lblocks + 1), &loffs, false, s));
+            SX_TRY(tmp.get(static_cast<size_t>(nls), &d_lslot, true, s));
+            hipLaunchKernelGGL(k_rb_mark_long, dim3(grid1d(nst)), dim3(SX_WG), 0, s, nst, rb->st, d_slice, d_cell_base, d_cell_e0,
+                               d_lbase, rb->chunks);
             hipLaunchKernelGGL(k_rb_long_fill, dim3(static_cast<unsigned>(nchunks)), dim3(SX_WG), 0, s, nchunks, rb->chunks, rb->idx,
-                               d_cnt2 + 1, lkey[0], lpay[0]);
+                               d_chbase, lkey[0], lpay[0], d_lslot);
             int cbits = 1;
             while ((static_cast<int64_t>(1) << cbits) < n) ++cbits;
             int lcur = 0;
-            SX_TRY(sx_sort_pairs(ctx, static_cast<int64_t>(nl), lkey, lpay, lhist, loffs, (cbits + 7) / 8, &lcur));
-            rb->nl = static_cast<int64_t>(nl);
-            SX_HIP(sx_dmalloc(reinterpret_cast<void **>(&rb->lcol), sizeof(int32_t) * static_cast<size_t>(nl)));
-            SX_HIP(sx_dmalloc(reinterpret_cast<void **>(&rb->le), sizeof(int32_t) * static_cast<size_t>(nl)));
-            SX_HIP(sx_dmalloc(reinterpret_cast<void **>(&rb->lval), sizeof(double) * static_cast<size_t>(nl)));
-            SX_HIP(sx_dmalloc(reinterpret_cast<void **>(&rb->lprod), sizeof(double) * static_cast<size_t>(nent + 8)));
-            SX_HIP(hipMemsetAsync(rb->lprod, 0, sizeof(double) * static_cast<size_t>(nent + 8), s));
-            hipLaunchKernelGGL(k_rb_long_lists, dim3(grid1d(static_cast<int64_t>(nl))), dim3(SX_WG), 0, s, static_cast<int64_t>(nl),
-                               lkey[lcur], lpay[lcur], rb->val, rb->lcol, rb->le, rb->lval);
+            SX_TRY(sx_sort_pairs(ctx, nl, lkey, lpay, lhist, loffs, (cbits + 7) / 8, &lcur));
+            rb->nl = nl;
+            rb->nls = nls;
+            SX_HIP(sx_dmalloc(reinterpret_cast<void **>(&rb->lcol), sizeof(int32_t) * static_cast<size_t>(nl + 8)));
+            SX_HIP(sx_dmalloc(reinterpret_cast<void **>(&rb->lperm), sizeof(uint16_t) * static_cast<size_t>(nl + 8)));
+            SX_HIP(sx_dmalloc(reinterpret_cast<void **>(&rb->lval), sizeof(double) * static_cast<size_t>(nl + 8)));
+            SX_HIP(sx_dmalloc(reinterpret_cast<void **>(&rb->lprod), sizeof(double) * static_cast<size_t>(nl + 8)));
+            SX_HIP(sx_dmalloc(reinterpret_cast<void **>(&rb->lsrc), sizeof(int32_t) * static_cast<size_t>(nls + 8)));
+            // (the pre-pass reads the lists in quads: the 8 entries behind the last one are column 0, value 0.0)
+            SX_HIP(hipMemsetAsync(rb->lcol + nl, 0, sizeof(int32_t) * 8, s));
+            SX_HIP(hipMemsetAsync(rb->lperm + nl, 0, sizeof(uint16_t) * 8, s));
+            SX_HIP(hipMemsetAsync(rb->lval + nl, 0, sizeof(double) * 8, s));
+            SX_HIP(hipMemsetAsync(rb->lprod, 0, sizeof(double) * static_cast<size_t>(nl + 8), s));
+            SX_HIP(hipMemsetAsync(rb->lsrc, 0, sizeof(int32_t) * static_cast<size_t>(nls + 8), s));
+            int sbits = 1, pbits = 1;
+            while ((static_cast<int64_t>(1) << sbits) < nls) ++sbits;
+            while ((static_cast<int64_t>(1) << pbits) < (nl + RB_PIECE - 1) / RB_PIECE) ++pbits;
+            uint64_t *key2[2] = {lkey[lcur ^ 1], lkey[lcur]};
+            int32_t *pay2[2] = {lpay[lcur ^ 1], lpay[lcur]};
+            hipLaunchKernelGGL(k_rb_long_lists, dim3(grid1d(nl)), dim3(SX_WG), 0, s, nl, lkey[lcur], lpay[lcur], d_lslot, rb->val,
+                               sbits, rb->lcol, rb->lval, key2[0], pay2[0]);
+            int cur2 = 0;
+            SX_TRY(sx_sort_pairs(ctx, nl, key2, pay2, lhist, loffs, (sbits + pbits + 7) / 8, &cur2));
+            hipLaunchKernelGGL(k_rb_long_perm, dim3(grid1d(nl)), dim3(SX_WG), 0, s, nl, key2[cur2], pay2[cur2], sbits, rb->lperm,
+                               rb->lsrc);
             SX_HIP(hipGetLastError());
-        } else if (nl > 0) { // too large for 32-bit slots: the chunks go back to the gather
-            SX_HIP(hipMemsetAsync(d_cnt2, 0, 2 * sizeof(unsigned long long), s));
+        } else if (nl > 0) { // too large for 32-bit slots: the long rows keep the gather
             rb->nl = -1;
         }
     }
@@ -489,7 +538,7 @@ int build(sx_ctx *ctx, const sx_matrix *A, bool force, sx_rowblock **out) {
 
 void sx_rowblock_free(sx_rowblock *rb) {
     if (!rb) return;
-    void *ptrs[10] = {rb->st, rb->chunks, rb->rowstart, rb->idx, rb->val, rb->lcol, rb->le, rb->lval, rb->lprod, rb->order};
+    void *ptrs[11] = {rb->st, rb->chunks, rb->rowstart, rb->idx, rb->val, rb->lcol, rb->lperm, rb->lsrc, rb->lval, rb->lprod, rb->order};
     for (void *p : ptrs)
         if (p) (void)sx_dfree(p);
     delete rb;
@@ -546,6 +595,36 @@ SX_API int sx_matrix_rowblock_download(sx_ctx *ctx, const sx_matrix *A, void *st
                               hipMemcpyDeviceToHost, s));
     if (idx) SX_HIP(hipMemcpyAsync(idx, rb->idx, sizeof(int32_t) * static_cast<size_t>(rb->nent + 8), hipMemcpyDeviceToHost, s));
     if (val) SX_HIP(hipMemcpyAsync(val, rb->val, sizeof(double) * static_cast<size_t>(rb->nent + 8), hipMemcpyDeviceToHost, s));
+    SX_HIP(hipStreamSynchronize(s));
+    return SX_OK;
+}
+
+// side arrays of the staged mode: info = {nl, nls, RB_PIECE} (nl <= 0: the long rows are gathered, nothing to download);
+// lcol / lval / lperm hold nl elements, lsrc nls + 8
+SX_API int sx_matrix_rowblock_long_info(sx_ctx *ctx, const sx_matrix *A, int64_t *info /* [3] */) {
+    SX_ENTER(ctx);
+    SX_REQUIRE(A != nullptr && info != nullptr, "NULL argument");
+    const sx_rowblock *rb = nullptr;
+    SX_TRY(sx_rowblock_get(ctx, A, &rb));
+    info[0] = rb ? rb->nl : 0;
+    info[1] = rb ? rb->nls : 0;
+    info[2] = RB_PIECE;
+    return SX_OK;
+}
+
+SX_API int sx_matrix_rowblock_long_download(sx_ctx *ctx, const sx_matrix *A, int32_t *lcol, double *lval, uint16_t *lperm,
+                                            int32_t *lsrc) {
+    SX_ENTER(ctx);
+    SX_REQUIRE(A != nullptr, "matrix is NULL");
+    const sx_rowblock *rb = nullptr;
+    SX_TRY(sx_rowblock_get(ctx, A, &rb));
+    SX_REQUIRE(rb != nullptr && rb->nl > 0, "the matrix has no staged long rows");
+    hipStream_t s = ctx->stream;
+    const size_t nl = static_cast<size_t>(rb->nl);
+    if (lcol) SX_HIP(hipMemcpyAsync(lcol, rb->lcol, sizeof(int32_t) * nl, hipMemcpyDeviceToHost, s));
+    if (lval) SX_HIP(hipMemcpyAsync(lval, rb->lval, sizeof(double) * nl, hipMemcpyDeviceToHost, s));
+    if (lperm) SX_HIP(hipMemcpyAsync(lperm, rb->lperm, sizeof(uint16_t) * nl, hipMemcpyDeviceToHost, s));
+    if (lsrc) SX_HIP(hipMemcpyAsync(lsrc, rb->lsrc, sizeof(int32_t) * static_cast<size_t>(rb->nls + 8), hipMemcpyDeviceToHost, s));
     SX_HIP(hipStreamSynchronize(s));
     return SX_OK;
 }

@@ -547,10 +547,20 @@ class DeviceMatrix:
         if nst == 0:
             return None
         out = dict(nst=nst, ncells=ncells, nchunks=nchunks, nent=nent, windowed=windowed, rs_stride=stride)
+        linfo = (C.c_int64 * 3)()
+        _l.check(self.ctx._lib.sx_matrix_rowblock_long_info(self.ctx.handle, self.handle, linfo))
+        nl, nls, piece = (int(v) for v in linfo)
+        out.update(nl=nl, nls=nls, piece=piece)          # nl > 0: the long rows are staged (option "rb_stage_long")
+        if download and nl > 0:
+            lcol, lval = np.zeros(nl, dtype=np.int32), np.zeros(nl, dtype=np.float64)
+            lperm, lsrc = np.zeros(nl, dtype=np.uint16), np.zeros(nls + 8, dtype=np.int32)
+            _l.check(self.ctx._lib.sx_matrix_rowblock_long_download(self.ctx.handle, self.handle, lcol.ctypes.data,
+                                                                    lval.ctypes.data, lperm.ctypes.data, lsrc.ctypes.data))
+            out.update(lcol=lcol, lval=lval, lperm=lperm, lsrc=lsrc)
         if download:
             st = np.zeros(nst, dtype=[("row0", "<i8"), ("chunk0", "<i8"), ("nrows", "<i4"), ("nchunks", "<i4")])
             ch = np.zeros(nchunks, dtype=[("e0", "<i8"), ("ne", "<i4"), ("col0", "<i4"), ("cell", "<i4"), ("base", "<i4"),
-                                          ("fresh", "<i4"), ("pad", "<i4")])
+                                          ("fresh", "<i4"), ("staged", "<i4")])
             rs = np.zeros(ncells * stride, dtype=np.uint16)
             idx = np.zeros(nent + 8, dtype=np.int32)
             val = np.zeros(nent + 8, dtype=np.float64)

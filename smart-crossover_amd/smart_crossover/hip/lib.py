@@ -103,6 +103,8 @@ PROTOTYPES = {
     "sx_matrix_rowblock_info": (_int, [_vp, _vp, _vp]),
     "sx_matrix_slabs_info": (_int, [_vp, _vp, _int, _vp]),
     "sx_matrix_rowblock_download": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sx_matrix_rowblock_long_info": (_int, [_vp, _vp, _vp]),
+    "sx_matrix_rowblock_long_download": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "sx_score_columns_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp]),
     "sx_score_columns": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp]),
     "sx_score_rows_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp]),

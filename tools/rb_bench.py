@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """K2 (and the CG row pass) over the column-blocked row layout vs the plain row walk, MI355X.
 
-    python tools/rb_bench.py [--m 1000000 --nb 10000000] [--structure staircase|uniform]
+    python tools/rb_bench.py [--m 1000000 --nb 10000000] [--structure staircase|uniform] [--workload shard|netlib]
+
+Three variants of one matrix in one process, timed in alternation: the plain walk, the layout with the long rows
+gathered in the walk (rb_stage_long 0) and with their products staged by the pre-pass (rb_stage_long 1).
 """
 import argparse
 import os
@@ -23,14 +26,20 @@ def main():
     ap.add_argument("--m", type=int, default=1_000_000)
     ap.add_argument("--nb", type=int, default=10_000_000)
     ap.add_argument("--structure", default="staircase")
+    ap.add_argument("--workload", default="shard", choices=["shard", "netlib"],
+                    help="netlib: workloads.netlib_lp(m, nb), all linking rows at the head of the LP")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
     t0 = time.time()
-    sh = workloads.lp_shard(0, 1, m=args.m, n_block=args.nb, k=8, structure=args.structure)
-    A = sh.row_block
+    if args.workload == "netlib":
+        sh = workloads.netlib_lp(args.m, args.nb)
+        A = sh.A
+    else:
+        sh = workloads.lp_shard(0, 1, m=args.m, n_block=args.nb, k=8, structure=args.structure)
+        A = sh.row_block
     m, n = A.shape
-    print(f"shard {A.shape} nnz={A.nnz} ({args.structure}) in {time.time() - t0:.1f}s", flush=True)
+    print(f"{args.workload} {A.shape} nnz={A.nnz} ({args.structure}) in {time.time() - t0:.1f}s", flush=True)
     ctx = Context(0)
     d_x, d_b, d_y = ctx.to_device(sh.x), ctx.to_device(sh.b), ctx.to_device(sh.y[:m])
     k2_bytes = 12 * A.nnz + 8 * n + 33 * m

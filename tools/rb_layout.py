@@ -2,6 +2,7 @@
 device builder is tested against, and the one tools/rb_bench.py uses for layout experiments.
 
     build(A_csr, R, cwin, chunk, dense_min, budget) -> dict of arrays (see sx_rowblock.h)
+    stage_long(layout, piece) -> side arrays of the staged long rows (option rb_stage_long)
 """
 from __future__ import annotations
 
@@ -148,8 +149,57 @@ def build(A: sp.csr_matrix, R: int = 1024, cwin: int = 4096, chunk: int = 4096, 
              "windowed_cells": int((cell_col0 != NO_WINDOW).sum()),
              "rowstart_bytes": int(rowstart.nbytes)}
     return {"st": st, "chunks": ch, "rowstart": rowstart, "rs_stride": stride, "idx": idx, "val": val, "stats": stats,
-            "R": R, "cwin": cwin, "chunk": chunk,
+            "R": R, "cwin": cwin, "chunk": chunk, "long_st": np.asarray(long_st, dtype=bool),
             "_cells": (cuts, st_nrows, cell_st, cell_ne, cell_e0, cell_col0)}
+
+
+PIECE = 8192         # long entries per piece of the product pre-pass (sx_rowblock.h RB_PIECE)
+
+
+def stage_long(L, piece: int = PIECE):
+    """Side arrays of the staged mode (option rb_stage_long; sx_rowblock.h): the products of the long rows come from
+    a pre-pass that streams their entries in column order, piece after piece, and writes the products of a piece in
+    the layout's own order, so that the walk finds the products of a chunk in a few contiguous runs.
+
+    The slots of the long super-tiles, one super-tile after the other, are the *long slots* 0 .. nls - 1
+    (``lslot[s]`` = the slot in idx / val; the gaps behind cells are among them).  Returns
+      staged   per chunk: 0, or 1 + the long slot of the chunk's first entry
+      lcol, lval, le   the nl long entries sorted by (column, slot): column, value, long slot
+      lperm    uint16: rank of list entry i among the entries of its piece (``piece`` consecutive list entries) by slot
+      lsrc     int32 per long slot: piece base + rank = where the pre-pass leaves that slot's product (0 for a gap)
+    """
+    cuts, st_nrows, cell_st, cell_ne, cell_e0, cell_col0 = L["_cells"]
+    long_st, st, ch = L["long_st"], L["st"], L["chunks"]
+    nst = cuts.size - 1
+    cells_per_st = np.bincount(cell_st, minlength=nst) if cell_ne.size else np.zeros(nst, dtype=np.int64)
+    st_cell0 = np.zeros(nst + 1, dtype=np.int64)
+    np.cumsum(cells_per_st, out=st_cell0[1:])
+    st_lo, st_hi = cell_e0[st_cell0[:-1]], cell_e0[st_cell0[1:]]
+    lbase = np.zeros(nst + 1, dtype=np.int64)
+    np.cumsum(np.where(long_st, st_hi - st_lo, 0), out=lbase[1:])
+    nls = int(lbase[-1])
+    longs = np.flatnonzero(long_st)
+    lslot = (np.concatenate([np.arange(st_lo[s], st_hi[s], dtype=np.int64) for s in longs]) if longs.size
+             else np.zeros(0, dtype=np.int64))
+    st_of_chunk = np.repeat(np.arange(nst, dtype=np.int64), st["nchunks"])
+    is_l = long_st[st_of_chunk] if ch.size else np.zeros(0, dtype=bool)
+    staged = np.zeros(ch.size, dtype=np.int32)
+    staged[is_l] = 1 + lbase[st_of_chunk[is_l]] + (ch["e0"][is_l] - st_lo[st_of_chunk[is_l]])
+    live = (np.concatenate([np.arange(s - 1, s - 1 + ne, dtype=np.int64) for s, ne in zip(staged[is_l], ch["ne"][is_l])])
+            if is_l.any() else np.zeros(0, dtype=np.int64))             # ascending: chunks are in slot order
+    col = L["idx"][lslot[live]]
+    order = np.argsort(col, kind="stable")                              # equal columns keep their slot order
+    le, lcol = live[order], col[order].astype(np.int32)
+    lval = L["val"][lslot[le]]
+    nl = le.size
+    by_slot = np.lexsort((le, np.arange(nl, dtype=np.int64) // piece))  # piece after piece, each in slot order
+    pos = np.empty(nl, dtype=np.int64)
+    pos[by_slot] = np.arange(nl, dtype=np.int64)
+    lperm = (pos % piece).astype(np.uint16)
+    lsrc = np.zeros(nls + 8, dtype=np.int32)
+    lsrc[le] = pos
+    return {"nl": nl, "nls": nls, "piece": piece, "staged": staged, "lslot": lslot, "lcol": lcol, "lval": lval,
+            "le": le, "lperm": lperm, "lsrc": lsrc}
 
 
 def _chunks(cuts, st_nrows, cell_st, cell_ne, cell_e0, cell_col0, chunk):
