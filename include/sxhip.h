@@ -62,10 +62,8 @@ int sx_ctx_create(int device, void *stream, sx_ctx **out);
 int sx_ctx_destroy(sx_ctx *ctx);
 int sx_ctx_sync(sx_ctx *ctx);
 /* Tuning knobs (performance only; the kernels of the scoring / pricing / CG path return identical bits
- * under every setting, the simplex the same optimum up to rounding): "xcd_swizzle" 0/1 (default 1), "nt_stream"
- * (cache policy of the streamed entry loads: 0 plain [default], 1 non-temporal, 2/16/17/18 buffer loads
- * with nt / sc1 / sc0 sc1 / nt sc1), "chunk" 2048/4096 (default 4096), "window" (LDS operand window of the
- * column walk in K1/K10: -1 auto [default: decided per matrix from its index clustering on first use],
+ * under every setting, the simplex the same optimum up to rounding): "xcd_swizzle" 0/1 (default 1),
+ * "window" (LDS operand window of the column walk in K1/K10: -1 auto [default: decided per matrix from its index clustering on first use],
  * 0 off, 1/2/4/8 tiles per window load), "graph" 0/1 (default 1: hipGraph replay of the CG iteration batch),
  * "rb_stage_long" (in the column-blocked row layout the products of the long rows -- the linking rows of an LP -- come
  * from a column-ordered pre-pass, which sorts them in LDS into the layout's order and writes them in whole lines, instead
@@ -76,8 +74,6 @@ int sx_ctx_sync(sx_ctx *ctx);
  * operand beyond 3.6 MB, one slab per 3.2 MB, at least 4M entries, carries no heavier than 1.25 x the entry stream; the
  * LDS window and the column-blocked rows are asked first], 0 never, 2..256 that many slabs; bit-identical either way --
  * a matrix with a segment whose indices descend somewhere keeps the plain walk),
- * "run_prefetch" (0/1, default 0: the windowed column walk with its loads one step ahead, csrc/sx_runwalk.h --
- * bit-identical, measured 4 % slower, kept as an experiment),
  * "spx_defer" (basis inverse of sx_simplex_solve*: 0 = rank-one update after every pivot, 1 = the updates
  * of a batch of 64 pivots are kept in product form and folded in as one rank-64 update by a hand-written kernel,
  * -1 auto [default]),

@@ -40,20 +40,6 @@ struct StageDot {
     }
 };
 
-__device__ __forceinline__ void walk_range(int64_t ntiles, int swizzle, int64_t &t, int64_t &t_end,
-                                           int64_t &t_step) {
-    t = blockIdx.x;
-    t_end = ntiles;
-    t_step = gridDim.x;
-    if (swizzle) {
-        const int64_t per = (ntiles + 7) >> 3;
-        t = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        t_end = ((blockIdx.x & 7) + 1) * per;
-        if (t_end > ntiles) t_end = ntiles;
-        t_step = gridDim.x >> 3;
-    }
-}
-
 // fixed-order block sum; result valid in thread 0
 __device__ __forceinline__ double block_sum(double v) {
     __shared__ double s[SX_WG / 64];
@@ -77,6 +63,14 @@ __device__ __forceinline__ double reduce_partials(const double *__restrict__ par
 }
 
 // out[j] = scale[j]^2 * (A^T in)[j]                                     (CSC pass)
+struct CgAtEpilogue { // load() requests the segment's operand before the walk streams its entries
+    const double *__restrict__ scale;
+    double *__restrict__ out;
+    double s;
+    __device__ __forceinline__ void load(int64_t seg, bool valid) { s = valid ? scale[seg] : 0.0; }
+    __device__ __forceinline__ void finish(int64_t j, double sum) const { out[j] = (s * s) * sum; }
+};
+
 __global__ __launch_bounds__(SX_WG) void k_cg_at(const CgState *st, const int64_t *__restrict__ tiles,
                                                  int64_t ntiles, int swizzle,
                                                  const int64_t *__restrict__ colptr,
@@ -87,18 +81,16 @@ __global__ __launch_bounds__(SX_WG) void k_cg_at(const CgState *st, const int64_
                                                  double *__restrict__ out) {
     if (st->done) return;
     __shared__ sx_walk_lds<1, CG_CHUNK> lds;
+    CgAtEpilogue epi{scale, out};
     int64_t t, t_end, t_step;
-    walk_range(ntiles, swizzle, t, t_end, t_step);
+    sx_walk_range(ntiles, swizzle, t, t_end, t_step);
     for (; t < t_end; t += t_step) {
         double acc[1];
         int64_t j;
         bool valid;
-        double s = 0.0;
-        auto pre = [&](int64_t seg, bool ok) {
-            if (ok) s = scale[seg];
-        };
+        auto pre = [&](int64_t seg, bool ok) { epi.load(seg, ok); };
         sx_segwalk<1, CG_CHUNK>(tiles, t, colptr, rowidx, val, StageDot{in}, lds, j, valid, acc, pre);
-        if (valid) out[j] = (s * s) * acc[0];
+        if (valid) epi.finish(j, acc[0]);
     }
 }
 
@@ -114,28 +106,10 @@ __global__ __launch_bounds__(SX_WG) void k_cg_at_lw(const CgState *st, const int
     if (st->done) return;
     __shared__ sx_walk_lds<1, SXL_CHUNK> lds;
     __shared__ double win[SXL_CAP];
-    const int64_t nruns = (ntiles + RUN - 1) / RUN;
+    CgAtEpilogue epi{scale, out};
     int64_t r, r_end, r_step;
-    walk_range(nruns, swizzle, r, r_end, r_step);
-    for (; r < r_end; r += r_step) {
-        const int64_t t0 = r * RUN;
-        const int64_t t1 = (t0 + RUN < ntiles) ? t0 + RUN : ntiles;
-        const int64_t wlo = win_lo[(t0 + t1 - 1) >> 1];
-        __syncthreads(); // the previous run's gathers are done with the window
-        sx_window_fill(win, in, wlo, m);
-        __syncthreads();
-        for (int64_t t = t0; t < t1; ++t) {
-            double acc[1];
-            int64_t j;
-            bool valid;
-            double s = 0.0;
-            auto pre = [&](int64_t seg, bool ok) {
-                if (ok) s = scale[seg];
-            };
-            sx_segwalk<1, SXL_CHUNK>(tiles, t, colptr, rowidx, val, sx_stage_win{in, win, wlo}, lds, j, valid, acc, pre);
-            if (valid) out[j] = (s * s) * acc[0];
-        }
-    }
+    sx_walk_range((ntiles + RUN - 1) / RUN, swizzle, r, r_end, r_step);
+    for (; r < r_end; r += r_step) sx_window_walk<RUN>(tiles, ntiles, r, win_lo, colptr, rowidx, val, in, m, lds, win, true, epi);
 }
 
 // q[i] = (A w)[i] + xs[i]^2 * p[i];  partial[block] = sum p[i]*q[i]       (CSR pass)
@@ -152,7 +126,7 @@ __global__ __launch_bounds__(SX_WG) void k_cg_a(const CgState *st, const int64_t
     if (st->done) return;
     __shared__ sx_walk_lds<1, CG_CHUNK> lds;
     int64_t t, t_end, t_step;
-    walk_range(ntiles, swizzle, t, t_end, t_step);
+    sx_walk_range(ntiles, swizzle, t, t_end, t_step);
     double dot = 0.0;
     for (; t < t_end; t += t_step) {
         double acc[1];
@@ -327,6 +301,19 @@ __global__ void k_cg_ones(int64_t n, double *v) {
         v[j] = 1.0;
 }
 
+// out = scale^2 .* (A^T in) on gT workgroups: behind the LDS operand window when win_run (sx_window_run_csc) says so
+void launch_cg_at(hipStream_t s, const CgState *st, const sx_matrix *A, int gT, int swzT, int win_run, const double *in,
+                  const double *scale, double *out) {
+    if (win_run >= 1)
+        sx_window_with_run<4, 1>(win_run, [&](auto R) {
+            hipLaunchKernelGGL(k_cg_at_lw<decltype(R)::value>, dim3(gT), dim3(SX_WG), 0, s, st, A->csc_tiles, A->n_csc_tiles,
+                               swzT, A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, A->m, in, scale, out);
+        });
+    else
+        hipLaunchKernelGGL(k_cg_at, dim3(gT), dim3(SX_WG), 0, s, st, A->csc_tiles, A->n_csc_tiles, swzT, A->csc_ptr,
+                           A->csc_idx, A->csc_val, in, scale, out);
+}
+
 inline int grid_for(const sx_ctx *ctx, int64_t ntiles) {
     int64_t g = ntiles < CG_GRID ? ntiles : CG_GRID;
     if (ctx->opt_xcd_swizzle && ntiles >= 64) g &= ~static_cast<int64_t>(7);
@@ -419,16 +406,8 @@ SX_API int sx_projector_std_dev(sx_ctx *ctx, const sx_matrix *A, const double *x
     double *r = z + m, *p = r + m, *q = p + m, *w = q + m, *atz = w + n;
     hipStream_t s = ctx->stream;
 
-    auto launch_at = [&](const double *in, const double *scale, double *out) { // out = scale^2 .* (A^T in)
-        if (win_run >= 4)
-            hipLaunchKernelGGL((k_cg_at_lw<4>), dim3(gT), dim3(SX_WG), 0, s, st, A->csc_tiles, A->n_csc_tiles, swzT,
-                               A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, m, in, scale, out);
-        else if (win_run >= 1)
-            hipLaunchKernelGGL((k_cg_at_lw<1>), dim3(gT), dim3(SX_WG), 0, s, st, A->csc_tiles, A->n_csc_tiles, swzT,
-                               A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, m, in, scale, out);
-        else
-            hipLaunchKernelGGL(k_cg_at, dim3(gT), dim3(SX_WG), 0, s, st, A->csc_tiles, A->n_csc_tiles, swzT, A->csc_ptr,
-                               A->csc_idx, A->csc_val, in, scale, out);
+    auto launch_at = [&](const double *in, const double *scale, double *out) {
+        launch_cg_at(s, st, A, gT, swzT, win_run, in, scale, out);
     };
     // row pass q = A w (+ xs^2 .* p), partials of p.q (or q.q) in ppq: over the column-blocked copy of the rows
     // when the matrix has one (sx_rowblock.h), else the plain walk; nA = number of partials either leaves
@@ -608,17 +587,7 @@ struct sx_cg_shard {
 namespace {
 
 void shard_at(sx_cg_shard *h, const double *in, const double *scale, double *out) {
-    const sx_matrix *A = h->A;
-    hipStream_t s = h->ctx->stream;
-    if (h->win_run >= 4)
-        hipLaunchKernelGGL((k_cg_at_lw<4>), dim3(h->gT), dim3(SX_WG), 0, s, h->st, A->csc_tiles, A->n_csc_tiles, h->swzT,
-                           A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, h->m, in, scale, out);
-    else if (h->win_run >= 1)
-        hipLaunchKernelGGL((k_cg_at_lw<1>), dim3(h->gT), dim3(SX_WG), 0, s, h->st, A->csc_tiles, A->n_csc_tiles, h->swzT,
-                           A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, h->m, in, scale, out);
-    else
-        hipLaunchKernelGGL(k_cg_at, dim3(h->gT), dim3(SX_WG), 0, s, h->st, A->csc_tiles, A->n_csc_tiles, h->swzT, A->csc_ptr,
-                           A->csc_idx, A->csc_val, in, scale, out);
+    launch_cg_at(h->ctx->stream, h->st, h->A, h->gT, h->swzT, h->win_run, in, scale, out);
 }
 
 int shard_a(sx_cg_shard *h, const double *vec, double *out) { // out = A_loc vec, partials of out.out in ppq

@@ -387,8 +387,7 @@ SX_API int sx_fixed_rhs_dev(sx_ctx *ctx, const sx_matrix *A, const uint8_t *code
     SX_REQUIRE(A->csr_ptr != nullptr, "matrix has no CSR layout");
     if (A->m == 0) return SX_OK;
     const int swz = ctx->opt_xcd_swizzle;
-    const unsigned grid = swz ? static_cast<unsigned>(((A->n_csr_tiles + 7) >> 3) << 3)
-                              : static_cast<unsigned>(A->n_csr_tiles);
+    const unsigned grid = sx_xcd_grid(A->n_csr_tiles, swz);
     hipLaunchKernelGGL(k_fixed_rhs, dim3(grid), dim3(SX_WG), 0, ctx->stream, A->csr_tiles, A->n_csr_tiles, swz,
                        A->csr_ptr, A->csr_idx, A->csr_val, code, u, l, b, b_sub);
     SX_HIP(hipGetLastError());

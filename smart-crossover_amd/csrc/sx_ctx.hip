@@ -163,15 +163,6 @@ SX_API int sx_ctx_set_option(sx_ctx *ctx, const char *key, int64_t value) {
     SX_REQUIRE(ctx != nullptr && key != nullptr, "ctx or key is NULL");
     if (!strcmp(key, "xcd_swizzle")) {
         ctx->opt_xcd_swizzle = value ? 1 : 0;
-    } else if (!strcmp(key, "nt_stream")) {
-        if (value != 0 && value != 1 && value != 2 && value != 16 && value != 17 && value != 18) {
-            sx_set_error("nt_stream must be 0, 1, 2, 16, 17 or 18");
-            return SX_ERR_INVALID;
-        }
-        ctx->opt_nt_stream = value;
-    } else if (!strcmp(key, "chunk")) {
-        SX_REQUIRE(value == 2048 || value == 4096, "chunk must be 2048 or 4096");
-        ctx->opt_chunk = static_cast<int>(value);
     } else if (!strcmp(key, "window")) {
         ctx->opt_window = value < 0 ? -1 : static_cast<int>(value);
     } else if (!strcmp(key, "netsimplex")) {
@@ -198,8 +189,6 @@ SX_API int sx_ctx_set_option(sx_ctx *ctx, const char *key, int64_t value) {
     } else if (!strcmp(key, "slabs")) {
         SX_REQUIRE(value >= -1 && value != 1 && value <= 256, "slabs must be -1 (auto), 0 (never) or 2..256");
         ctx->opt_slabs = static_cast<int>(value);
-    } else if (!strcmp(key, "run_prefetch")) {
-        ctx->opt_run_prefetch = value ? 1 : 0;
     } else if (!strcmp(key, "rb_long_xcd")) {
         SX_REQUIRE(value >= -1 && value <= 1, "rb_long_xcd must be -1 (auto), 0 (never) or 1 (always)");
         ctx->opt_rb_long_xcd = static_cast<int>(value);

@@ -91,8 +91,6 @@ struct sx_ctx {
     std::vector<hipEvent_t> markers;
     // tuning knobs (sx_ctx_set_option); defaults are the measured best on MI355X
     int opt_xcd_swizzle = 1; // XCD-contiguous block -> tile map
-    int opt_nt_stream = 0;   // non-temporal loads for the streamed entry arrays
-    int opt_chunk = 4096;    // staged entries per chunk (2048 or 4096)
     int opt_window = -1;     // LDS operand window of the column walk: -1 auto, 0 off, 1/2/4/8 tiles per load
     int opt_graph = 1;       // replay the CG iteration batch as a hipGraph
     int opt_spx_defer = -1;  // K16 basis inverse: -1 auto, 0 rank-one update per pivot, 1 rank-32 update per batch
@@ -106,7 +104,6 @@ struct sx_ctx {
     int opt_nd_grid = 0;     // K16d: workgroups of its cooperative grid (0: by size)
     int opt_spx_pricing = 1; // K16 entering variable: 0 Dantzig (largest reduced cost), 1 Devex reference weights
     int opt_slabs = -1;        // operand slabs of a walk without locality (sx_slabs.h): -1 auto, 0 never, R >= 2: R slabs
-    int opt_run_prefetch = 0;  // windowed column walk (K1, K10): loads one step ahead (sx_runwalk.h); 0: tile by tile
     int opt_rb_long_xcd = -1;  // row-blocked walks: the long-row super-tiles dealt over the XCDs (sx_rowblock.h: order[]): -1 when the
                                // matrix puts them unevenly, 0 never, 1 always
     int opt_rb_dense_min = 512; // entries from which a column block of a super-tile gets an LDS window (read when a layout is built;
@@ -212,6 +209,11 @@ constexpr double SX_SWIZZLE_MAX_IMBALANCE = 1.5;
 // window_autotune (sx_lp_kernels.hip) found this matrix faster without it
 inline int sx_csc_swizzle(const sx_ctx *ctx, const sx_matrix *A) {
     return (ctx->opt_xcd_swizzle && A->n_csc_tiles >= 64 && !A->csc_swizzle_off) ? 1 : 0;
+}
+// grid of a launch with one workgroup per item: under the XCD-contiguous map (sx_tile_of_block, sx_segwalk.h) every XCD
+// gets ceil(n / 8) slots, and the workgroups of the last slots that map past n return at once
+inline unsigned sx_xcd_grid(int64_t n, int swizzle) {
+    return static_cast<unsigned>(swizzle ? ((n + 7) >> 3) << 3 : n);
 }
 // exclusive scan of in[0..n) into out[0..n] (out[n] = total); uses ctx->ws (sx_compact.hip)
 int sx_scan_exclusive(sx_ctx *ctx, const int64_t *in, int64_t n, int64_t *out);

@@ -5,7 +5,7 @@
 #include "sx_internal.h"
 #include "sx_rowblock.h"
 #include "sx_segwalk.h"
-#include "sx_runwalk.h"
+#include "sx_window.h"
 #include "sx_slabs.h"
 
 #include <cmath>
@@ -19,25 +19,20 @@ struct StageDot {
     }
 };
 
+constexpr int LP_CHUNK = 4096; // staged entries per chunk of the plain walks (2048: 2-19 % slower, profiles/r01/kbench_tuning_knobs.txt)
+
 // ------------------------------------------------------------------------------------- K1
-template <int CHUNK, int NT>
-__global__ __launch_bounds__(SX_WG) void k_score_columns(
-    const int64_t *__restrict__ tiles, int64_t ntiles, int swizzle,
-    const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx,
-    const double *__restrict__ val, const double *__restrict__ y, const double *__restrict__ c,
-    const double *__restrict__ x, const double *__restrict__ l, const double *__restrict__ u,
-    double gamma, double *__restrict__ s_d, uint8_t *__restrict__ code, const double *__restrict__ carry_in) {
-    __shared__ sx_walk_lds<1, CHUNK> lds;
-    const int64_t tile = sx_tile_of_block(blockIdx.x, ntiles, swizzle);
-    if (tile >= ntiles) return;
-    double acc[1] = {0.0};
-    int64_t j;
-    bool valid;
-    // the epilogue's operands are requested before the walk so their latency hides under it
-    double cj = 0.0, xj = 0.0, lj = 0.0, uj = 0.0;
-    auto pre = [&](int64_t seg, bool ok) {
-        if (ok) {
-            if (carry_in) acc[0] = carry_in[seg]; // last slab of a slabbed walk (sx_slabs.h): the sum continues
+// The epilogue of K1: sd = c - sum, and the column's code bits from x, l, u.  load() requests the operands of the lane's
+// segment -- the walks call it before any entry is streamed, so that their latency hides under the walk.
+struct ScoreColumnsEpilogue {
+    const double *__restrict__ c, *__restrict__ x, *__restrict__ l, *__restrict__ u;
+    double gamma;
+    double *__restrict__ s_d;
+    uint8_t *__restrict__ code;
+    double cj, xj, lj, uj;
+    __device__ __forceinline__ void load(int64_t seg, bool valid) {
+        cj = xj = lj = uj = 0.0;
+        if (valid) {
             cj = c[seg];
             if (code) {
                 xj = x[seg];
@@ -45,26 +40,48 @@ __global__ __launch_bounds__(SX_WG) void k_score_columns(
                 uj = u[seg];
             }
         }
-    };
-    sx_segwalk<1, CHUNK, NT>(tiles, tile, colptr, rowidx, val, StageDot{y}, lds, j, valid, acc, pre, true);
-    if (!valid) return;
-    const double sd = cj - acc[0];
-    if (s_d) s_d[j] = sd;
-    if (code) {
-        const bool low = (xj - lj) < (gamma * sd);
-        const bool up = (uj - xj) < (gamma * (-sd));
-        code[j] = static_cast<uint8_t>((low ? SX_CODE_LOW : 0u) | (up ? SX_CODE_UP : 0u));
     }
+    __device__ __forceinline__ void finish(int64_t j, double sum) const {
+        const double sd = cj - sum;
+        if (s_d) s_d[j] = sd;
+        if (code) {
+            const bool low = (xj - lj) < (gamma * sd);
+            const bool up = (uj - xj) < (gamma * (-sd));
+            code[j] = static_cast<uint8_t>((low ? SX_CODE_LOW : 0u) | (up ? SX_CODE_UP : 0u));
+        }
+    }
+};
+
+template <int NT>
+__global__ __launch_bounds__(SX_WG) void k_score_columns(
+    const int64_t *__restrict__ tiles, int64_t ntiles, int swizzle,
+    const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx,
+    const double *__restrict__ val, const double *__restrict__ y, const double *__restrict__ c,
+    const double *__restrict__ x, const double *__restrict__ l, const double *__restrict__ u,
+    double gamma, double *__restrict__ s_d, uint8_t *__restrict__ code, const double *__restrict__ carry_in) {
+    __shared__ sx_walk_lds<1, LP_CHUNK> lds;
+    const int64_t tile = sx_tile_of_block(blockIdx.x, ntiles, swizzle);
+    if (tile >= ntiles) return;
+    double acc[1] = {0.0};
+    int64_t j;
+    bool valid;
+    ScoreColumnsEpilogue epi{c, x, l, u, gamma, s_d, code};
+    auto pre = [&](int64_t seg, bool ok) {
+        if (ok && carry_in) acc[0] = carry_in[seg]; // last slab of a slabbed walk (sx_slabs.h): the sum continues
+        epi.load(seg, ok);
+    };
+    sx_segwalk<1, LP_CHUNK, NT>(tiles, tile, colptr, rowidx, val, StageDot{y}, lds, j, valid, acc, pre, true);
+    if (valid) epi.finish(j, acc[0]);
 }
 
 // A pass of a slabbed walk that is not the last one (sx_slabs.h): carry[seg] (+0.0 in the first pass) continued by
-// the slab's products, left to right.  Serves the column and the row walk alike.
-template <int CHUNK, int NT>
+// the slab's products, left to right.  Serves the column and the row walk alike.  The entry stream is read once and
+// non-temporal (stream policy 2), so that it does not displace the operand slab from L2.
 __global__ __launch_bounds__(SX_WG) void k_slab_accumulate(
     const int64_t *__restrict__ tiles, int64_t ntiles, int swizzle, const int64_t *__restrict__ ptr,
     const int32_t *__restrict__ idx, const double *__restrict__ val, const double *__restrict__ operand,
     int first, double *__restrict__ carry) {
-    __shared__ sx_walk_lds<1, CHUNK> lds;
+    __shared__ sx_walk_lds<1, LP_CHUNK> lds;
     const int64_t tile = sx_tile_of_block(blockIdx.x, ntiles, swizzle);
     if (tile >= ntiles) return;
     double acc[1] = {0.0};
@@ -73,13 +90,13 @@ __global__ __launch_bounds__(SX_WG) void k_slab_accumulate(
     auto pre = [&](int64_t sg, bool ok) {
         if (ok && !first) acc[0] = carry[sg];
     };
-    sx_segwalk<1, CHUNK, NT>(tiles, tile, ptr, idx, val, StageDot{operand}, lds, seg, valid, acc, pre, true);
+    sx_segwalk<1, LP_CHUNK, 2>(tiles, tile, ptr, idx, val, StageDot{operand}, lds, seg, valid, acc, pre, true);
     if (valid) carry[seg] = acc[0];
 }
 
 // K1 behind an LDS operand window: one workgroup scores RUN consecutive tiles per window load
 // (sx_window.h).  Same sums, same roundings, same outputs as k_score_columns.
-template <int RUN, int PF>
+template <int RUN>
 __global__ __launch_bounds__(SX_WG) void k_score_columns_lw(
     const int64_t *__restrict__ tiles, int64_t ntiles, int swizzle, const int32_t *__restrict__ win_lo,
     const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx, const double *__restrict__ val,
@@ -91,75 +108,19 @@ __global__ __launch_bounds__(SX_WG) void k_score_columns_lw(
     const int64_t nruns = (ntiles + RUN - 1) / RUN;
     const int64_t run = sx_tile_of_block(blockIdx.x, nruns, swizzle);
     if (run >= nruns) return;
-    const int64_t t0 = run * RUN;
-    const int64_t t1 = (t0 + RUN < ntiles) ? t0 + RUN : ntiles;
-    const int64_t wlo = win_lo[(t0 + t1 - 1) >> 1]; // window of the run's middle tile
-    sx_window_fill(win, y, wlo, m);
-    __syncthreads();
-    if constexpr (PF) { // loads one step ahead (sx_runwalk.h)
-        struct Ops {
-            double cj, xj, lj, uj;
-        };
-        auto pre = [&](int64_t seg) {
-            Ops o{c[seg], 0.0, 0.0, 0.0};
-            if (code) { // uniform
-                o.xj = x[seg];
-                o.lj = l[seg];
-                o.uj = u[seg];
-            }
-            return o;
-        };
-        auto epi = [&](int64_t j, bool valid, double sum, const Ops &o) {
-            if (!valid) return;
-            const double sd = o.cj - sum;
-            if (s_d) s_d[j] = sd;
-            if (code) {
-                const bool low = (o.xj - o.lj) < (gamma * sd);
-                const bool up = (o.uj - o.xj) < (gamma * (-sd));
-                code[j] = static_cast<uint8_t>((low ? SX_CODE_LOW : 0u) | (up ? SX_CODE_UP : 0u));
-            }
-        };
-        sx_runwalk<RUN>(tiles, t0, t1, colptr, rowidx, val, sx_stage_win{y, win, wlo}, lds, pre, epi);
-        return;
-    }
-    for (int64_t tile = t0; tile < t1; ++tile) {
-        double acc[1];
-        int64_t j;
-        bool valid;
-        double cj = 0.0, xj = 0.0, lj = 0.0, uj = 0.0;
-        auto pre = [&](int64_t seg, bool ok) {
-            if (ok) {
-                cj = c[seg];
-                if (code) {
-                    xj = x[seg];
-                    lj = l[seg];
-                    uj = u[seg];
-                }
-            }
-        };
-        sx_segwalk<1, SXL_CHUNK, 0>(tiles, tile, colptr, rowidx, val, sx_stage_win{y, win, wlo}, lds, j, valid,
-                                    acc, pre);
-        if (valid) {
-            const double sd = cj - acc[0];
-            if (s_d) s_d[j] = sd;
-            if (code) {
-                const bool low = (xj - lj) < (gamma * sd);
-                const bool up = (uj - xj) < (gamma * (-sd));
-                code[j] = static_cast<uint8_t>((low ? SX_CODE_LOW : 0u) | (up ? SX_CODE_UP : 0u));
-            }
-        }
-    }
+    ScoreColumnsEpilogue epi{c, x, l, u, gamma, s_d, code};
+    sx_window_walk<RUN>(tiles, ntiles, run, win_lo, colptr, rowidx, val, y, m, lds, win, false, epi);
 }
 
 // ------------------------------------------------------------------------------------- K2
-template <int CHUNK, int NT>
+template <int NT>
 __global__ __launch_bounds__(SX_WG) void k_score_rows(
     const int64_t *__restrict__ tiles, int64_t ntiles, int swizzle,
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
     const double *__restrict__ val, const double *__restrict__ x, const double *__restrict__ b,
     const double *__restrict__ y, double gamma_dual, double *__restrict__ s_p,
     uint8_t *__restrict__ flag, const double *__restrict__ carry_in) {
-    __shared__ sx_walk_lds<1, CHUNK> lds;
+    __shared__ sx_walk_lds<1, LP_CHUNK> lds;
     const int64_t tile = sx_tile_of_block(blockIdx.x, ntiles, swizzle);
     if (tile >= ntiles) return;
     double acc[1] = {0.0};
@@ -173,7 +134,7 @@ __global__ __launch_bounds__(SX_WG) void k_score_rows(
             if (flag) yi = y[seg];
         }
     };
-    sx_segwalk<1, CHUNK, NT>(tiles, tile, rowptr, colidx, val, StageDot{x}, lds, i, valid, acc, pre, true);
+    sx_segwalk<1, LP_CHUNK, NT>(tiles, tile, rowptr, colidx, val, StageDot{x}, lds, i, valid, acc, pre, true);
     if (!valid) return;
     const double sp = bi - acc[0];
     if (s_p) s_p[i] = sp;
@@ -227,57 +188,65 @@ __device__ __forceinline__ void price_block_reduce(double v, long long ix, long 
     }
 }
 
+// The epilogue of K10: rc = c - sum (sign flipped at the upper bound), and the lane's running partial -- the smallest
+// reduced cost it has seen, where, and how many violate the tolerance.  load() as in K1.
+struct PriceEpilogue {
+    const double *__restrict__ c;
+    const int8_t *__restrict__ vbasis;
+    double tol;
+    double *__restrict__ rc_out;
+    double v = 0.0;
+    long long ix = -1, bad = 0;
+    double cj;
+    int vbj;
+    __device__ __forceinline__ void load(int64_t seg, bool valid) {
+        cj = 0.0;
+        vbj = 0;
+        if (valid) {
+            cj = c[seg];
+            if (vbasis) vbj = vbasis[seg];
+        }
+    }
+    __device__ __forceinline__ void finish(int64_t j, double sum) {
+        double rc = cj - sum;
+        if (vbj == -2) rc = -rc;
+        if (rc_out) rc_out[j] = rc;
+        bad += (rc >= -tol) ? 0 : 1;
+        if (rc == rc) price_combine(v, ix, rc, j); // NaN never becomes the minimum
+    }
+};
+
 // grid-stride over tiles: one partial per workgroup (at most PRICE_GRID of them)
 constexpr int PRICE_GRID = 2048;
 
-template <int CHUNK, int NT>
+template <int NT>
 __global__ __launch_bounds__(SX_WG) void k_price(
     const int64_t *__restrict__ tiles, int64_t ntiles, int swizzle,
     const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx,
     const double *__restrict__ val, const double *__restrict__ y, const double *__restrict__ c,
     const int8_t *__restrict__ vbasis, double tol, double *__restrict__ rc_out,
     PricePartial *__restrict__ partial, const double *__restrict__ carry_in) {
-    __shared__ sx_walk_lds<1, CHUNK> lds;
-    double v = 0.0;
-    long long ix = -1, bad = 0;
-    // tile range and stride of this workgroup: with the XCD swizzle (gridDim.x is a multiple of 8)
-    // XCD k = blockIdx % 8 walks the contiguous range [k*per, (k+1)*per) with its gridDim/8 blocks
-    int64_t t = blockIdx.x, t_end = ntiles, t_step = gridDim.x;
-    if (swizzle) {
-        const int64_t per = (ntiles + 7) >> 3;
-        t = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        t_end = ((blockIdx.x & 7) + 1) * per;
-        if (t_end > ntiles) t_end = ntiles;
-        t_step = gridDim.x >> 3;
-    }
+    __shared__ sx_walk_lds<1, LP_CHUNK> lds;
+    PriceEpilogue epi{c, vbasis, tol, rc_out};
+    int64_t t, t_end, t_step;
+    sx_walk_range(ntiles, swizzle, t, t_end, t_step);
     for (; t < t_end; t += t_step) {
         double acc[1] = {0.0};
         int64_t j;
         bool valid;
-        double cj = 0.0;
-        int vbj = 0; // requested before the walk so that their latency hides under it
         auto pre = [&](int64_t seg, bool ok) {
-            if (ok) {
-                if (carry_in) acc[0] = carry_in[seg]; // last slab of a slabbed walk (sx_slabs.h)
-                cj = c[seg];
-                if (vbasis) vbj = vbasis[seg];
-            }
+            if (ok && carry_in) acc[0] = carry_in[seg]; // last slab of a slabbed walk (sx_slabs.h)
+            epi.load(seg, ok);
         };
-        sx_segwalk<1, CHUNK, NT>(tiles, t, colptr, rowidx, val, StageDot{y}, lds, j, valid, acc, pre, true);
-        if (valid) {
-            double rc = cj - acc[0];
-            if (vbj == -2) rc = -rc;
-            if (rc_out) rc_out[j] = rc;
-            bad += (rc >= -tol) ? 0 : 1;
-            if (rc == rc) price_combine(v, ix, rc, j); // NaN never becomes the minimum
-        }
+        sx_segwalk<1, LP_CHUNK, NT>(tiles, t, colptr, rowidx, val, StageDot{y}, lds, j, valid, acc, pre, true);
+        if (valid) epi.finish(j, acc[0]);
     }
     __syncthreads(); // the last tile's sums are out of the product buffer
-    price_block_reduce(v, ix, bad, &partial[blockIdx.x], lds.v[0]);
+    price_block_reduce(epi.v, epi.ix, epi.bad, &partial[blockIdx.x], lds.v[0]);
 }
 
 // K10 behind the LDS operand window: grid-stride over runs of RUN tiles, one window load per run
-template <int RUN, int PF>
+template <int RUN>
 __global__ __launch_bounds__(SX_WG, 4) void k_price_lw(
     const int64_t *__restrict__ tiles, int64_t ntiles, int swizzle, const int32_t *__restrict__ win_lo,
     const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowidx, const double *__restrict__ val,
@@ -285,70 +254,12 @@ __global__ __launch_bounds__(SX_WG, 4) void k_price_lw(
     double tol, double *__restrict__ rc_out, PricePartial *__restrict__ partial) {
     __shared__ sx_walk_lds<1, SXL_CHUNK> lds;
     __shared__ double win[SXL_CAP];
-    double v = 0.0;
-    long long ix = -1, bad = 0;
-    const int64_t nruns = (ntiles + RUN - 1) / RUN;
-    int64_t r = blockIdx.x, r_end = nruns, r_step = gridDim.x;
-    if (swizzle) { // gridDim.x is a multiple of 8: XCD k walks the contiguous runs [k*per, (k+1)*per)
-        const int64_t per = (nruns + 7) >> 3;
-        r = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        r_end = ((blockIdx.x & 7) + 1) * per;
-        if (r_end > nruns) r_end = nruns;
-        r_step = gridDim.x >> 3;
-    }
-    for (; r < r_end; r += r_step) {
-        const int64_t t0 = r * RUN;
-        const int64_t t1 = (t0 + RUN < ntiles) ? t0 + RUN : ntiles;
-        const int64_t wlo = win_lo[(t0 + t1 - 1) >> 1];
-        __syncthreads(); // the previous run's gathers are done with the window
-        sx_window_fill(win, y, wlo, m);
-        __syncthreads();
-        if constexpr (PF) { // loads one step ahead (sx_runwalk.h)
-            struct Ops {
-                double cj;
-                int vbj;
-            };
-            auto pre = [&](int64_t seg) {
-                Ops o{c[seg], 0};
-                if (vbasis) o.vbj = vbasis[seg]; // uniform
-                return o;
-            };
-            auto epi = [&](int64_t j, bool valid, double sum, const Ops &o) {
-                if (!valid) return;
-                double rc = o.cj - sum;
-                if (o.vbj == -2) rc = -rc;
-                if (rc_out) rc_out[j] = rc;
-                bad += (rc >= -tol) ? 0 : 1;
-                if (rc == rc) price_combine(v, ix, rc, j);
-            };
-            sx_runwalk<RUN>(tiles, t0, t1, colptr, rowidx, val, sx_stage_win{y, win, wlo}, lds, pre, epi);
-            continue;
-        }
-        for (int64_t t = t0; t < t1; ++t) {
-            double acc[1];
-            int64_t j;
-            bool valid;
-            double cj = 0.0;
-            int vbj = 0; // the epilogue's operands are requested before the walk (as in K1)
-            auto pre = [&](int64_t seg, bool ok) {
-                if (ok) {
-                    cj = c[seg];
-                    if (vbasis) vbj = vbasis[seg];
-                }
-            };
-            sx_segwalk<1, SXL_CHUNK, 0>(tiles, t, colptr, rowidx, val, sx_stage_win{y, win, wlo}, lds, j, valid, acc,
-                                        pre);
-            if (valid) {
-                double rc = cj - acc[0];
-                if (vbj == -2) rc = -rc;
-                if (rc_out) rc_out[j] = rc;
-                bad += (rc >= -tol) ? 0 : 1;
-                if (rc == rc) price_combine(v, ix, rc, j);
-            }
-        }
-    }
+    PriceEpilogue epi{c, vbasis, tol, rc_out};
+    int64_t r, r_end, r_step;
+    sx_walk_range((ntiles + RUN - 1) / RUN, swizzle, r, r_end, r_step);
+    for (; r < r_end; r += r_step) sx_window_walk<RUN>(tiles, ntiles, r, win_lo, colptr, rowidx, val, y, m, lds, win, true, epi);
     __syncthreads(); // the last tile's sums are out of the product buffer
-    price_block_reduce(v, ix, bad, &partial[blockIdx.x], lds.v[0]);
+    price_block_reduce(epi.v, epi.ix, epi.bad, &partial[blockIdx.x], lds.v[0]);
 }
 
 __global__ __launch_bounds__(SX_WG) void k_price_final(const PricePartial *__restrict__ partial,
@@ -549,40 +460,58 @@ __global__ __launch_bounds__(SX_WG) void k_mask_f64(int64_t n, const double *__r
         dst[i] = mask[i] ? src[i] : 0.0;
 }
 
-// grid of a one-tile-per-workgroup launch: with the XCD swizzle every XCD gets ceil(T/8) slots
-inline unsigned walk_grid(const sx_ctx *ctx, int64_t ntiles) {
-    if (!ctx->opt_xcd_swizzle) return static_cast<unsigned>(ntiles);
-    return static_cast<unsigned>(((ntiles + 7) >> 3) << 3);
-}
+// grid of a one-tile-per-workgroup launch under the context's XCD option (the kernel's own `swizzle` may still be 0:
+// the workgroups past the last tile return at once)
+inline unsigned walk_grid(const sx_ctx *ctx, int64_t ntiles) { return sx_xcd_grid(ntiles, ctx->opt_xcd_swizzle); }
 
-// passes 0 .. R-2 of a slabbed walk: S->carry holds the running sums the last pass starts from.  The entry stream is
-// read once and non-temporal, so that it does not displace the operand slab from L2.
+// passes 0 .. R-2 of a slabbed walk: S->carry holds the running sums the last pass starts from
 static int slab_passes(sx_ctx *ctx, const sx_slabs *S, const double *operand) {
     for (int s = 0; s + 1 < S->R; ++s) {
         const sx_slab &L = S->slab[s];
-        hipLaunchKernelGGL((k_slab_accumulate<4096, 2>), dim3(walk_grid(ctx, L.ntiles)), dim3(SX_WG), 0, ctx->stream, L.tiles,
+        hipLaunchKernelGGL(k_slab_accumulate, dim3(walk_grid(ctx, L.ntiles)), dim3(SX_WG), 0, ctx->stream, L.tiles,
                            L.ntiles, ctx->opt_xcd_swizzle, L.ptr, L.idx, L.val, operand + L.off, s == 0 ? 1 : 0, S->carry);
     }
     SX_HIP(hipGetLastError());
     return SX_OK;
 }
 
-#define SX_DISPATCH_VARIANT(ctx, LAUNCH)                                                           \
-    do {                                                                                           \
-        if ((ctx)->opt_chunk == 2048) {                                                            \
-            if ((ctx)->opt_nt_stream) LAUNCH(2048, 1);                                             \
-            else LAUNCH(2048, 0);                                                                  \
-        } else {                                                                                   \
-            switch ((ctx)->opt_nt_stream) {                                                        \
-            case 1: LAUNCH(4096, 1); break;                                                        \
-            case 2: LAUNCH(4096, 2); break;                                                        \
-            case 16: LAUNCH(4096, 16); break;                                                      \
-            case 17: LAUNCH(4096, 17); break;                                                      \
-            case 18: LAUNCH(4096, 18); break;                                                      \
-            default: LAUNCH(4096, 0); break;                                                       \
-            }                                                                                      \
-        }                                                                                          \
-    } while (0)
+// K1 behind the window, `run` tiles per window load
+static void launch_score_columns_lw(sx_ctx *ctx, const sx_matrix *A, int run, int swz, const double *y, const double *c,
+                                    const double *x, const double *l, const double *u, double gamma, double *s_d,
+                                    uint8_t *code) {
+    sx_window_with_run<8, 4, 2, 1>(run, [&](auto R) {
+        constexpr int RUN = decltype(R)::value;
+        const int64_t nruns = (A->n_csc_tiles + RUN - 1) / RUN;
+        hipLaunchKernelGGL(k_score_columns_lw<RUN>, dim3(walk_grid(ctx, nruns)), dim3(SX_WG), 0, ctx->stream,
+                           A->csc_tiles, A->n_csc_tiles, swz, A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, A->m, y,
+                           c, x, l, u, gamma, s_d, code);
+    });
+}
+
+// K10 behind the window, `run` tiles per window load, on nb workgroups
+static void launch_price_lw(sx_ctx *ctx, const sx_matrix *A, int run, int swz, int nb, const double *y, const double *c,
+                            const int8_t *vbasis, double tol, double *rc, PricePartial *partial) {
+    sx_window_with_run<8, 4, 2, 1>(run, [&](auto R) {
+        hipLaunchKernelGGL(k_price_lw<decltype(R)::value>, dim3(nb), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles, swz,
+                           A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, A->m, y, c, vbasis, tol, rc, partial);
+    });
+}
+
+// One pricing over `ntiles` tiles: walk(nb, partial) enqueues the walk kernel on nb workgroups -- at most PRICE_GRID, a
+// multiple of 8 when the walk uses the XCD map (`mult8`; callers ask for that from 64 tiles on only) -- which leave one
+// partial each in the context's workspace; k_price_final folds them into *result_dev (nullptr: the walk alone).
+template <class Walk>
+static int price_launch(sx_ctx *ctx, int64_t ntiles, int mult8, sx_price_result *result_dev, Walk walk) {
+    int nb = static_cast<int>(ntiles < PRICE_GRID ? ntiles : PRICE_GRID);
+    if (mult8) nb &= ~7;
+    SX_TRY(sx_reserve(ctx, static_cast<size_t>(nb) * sizeof(PricePartial)));
+    PricePartial *partial = static_cast<PricePartial *>(ctx->ws);
+    walk(nb, partial);
+    if (result_dev)
+        hipLaunchKernelGGL(k_price_final, dim3(1), dim3(SX_WG), 0, ctx->stream, partial, static_cast<int64_t>(nb), result_dev);
+    SX_HIP(hipGetLastError());
+    return SX_OK;
+}
 
 } // namespace
 
@@ -646,11 +575,9 @@ SX_API int sx_score_columns_dev(sx_ctx *ctx, const sx_matrix *A, const double *y
     int run = 0; // LDS operand window (sx_window.h): table built on first use; a large matrix is timed once, else the rule decides
     SX_TRY(window_autotune(ctx, A, [&](int windowed, int swz) -> int {
         if (windowed) {
-            const int64_t nruns = (A->n_csc_tiles + 3) / 4;
-            hipLaunchKernelGGL((k_score_columns_lw<4, 0>), dim3(walk_grid(ctx, nruns)), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles, swz,
-                               A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, A->m, y, c, x, l, u, gamma, s_d, code);
+            launch_score_columns_lw(ctx, A, 4, swz, y, c, x, l, u, gamma, s_d, code);
         } else {
-            hipLaunchKernelGGL((k_score_columns<4096, 0>), dim3(walk_grid(ctx, A->n_csc_tiles)), dim3(SX_WG), 0, ctx->stream, A->csc_tiles,
+            hipLaunchKernelGGL(k_score_columns<0>, dim3(walk_grid(ctx, A->n_csc_tiles)), dim3(SX_WG), 0, ctx->stream, A->csc_tiles,
                                A->n_csc_tiles, swz, A->csc_ptr, A->csc_idx, A->csc_val, y, c, x, l, u, gamma, s_d, code,
                                static_cast<const double *>(nullptr));
         }
@@ -658,26 +585,7 @@ SX_API int sx_score_columns_dev(sx_ctx *ctx, const sx_matrix *A, const double *y
     }));
     SX_TRY(sx_window_run_csc(ctx, A, &run));
     if (run) {
-        const int swz = sx_csc_swizzle(ctx, A);
-#define SX_LAUNCH_K1W(R)                                                                           \
-    do {                                                                                           \
-        const int64_t nruns = (A->n_csc_tiles + (R)-1) / (R);                                      \
-        if (ctx->opt_run_prefetch)                                                                 \
-            hipLaunchKernelGGL((k_score_columns_lw<R, 1>), dim3(walk_grid(ctx, nruns)), dim3(SX_WG), 0, \
-                               ctx->stream, A->csc_tiles, A->n_csc_tiles, swz, A->csc_win_lo,      \
-                               A->csc_ptr, A->csc_idx, A->csc_val, A->m, y, c, x, l, u, gamma, s_d, \
-                               code);                                                              \
-        else                                                                                       \
-            hipLaunchKernelGGL((k_score_columns_lw<R, 0>), dim3(walk_grid(ctx, nruns)), dim3(SX_WG), 0, \
-                               ctx->stream, A->csc_tiles, A->n_csc_tiles, swz, A->csc_win_lo,      \
-                               A->csc_ptr, A->csc_idx, A->csc_val, A->m, y, c, x, l, u, gamma, s_d, \
-                               code);                                                              \
-    } while (0)
-        if (run == 8) SX_LAUNCH_K1W(8);
-        else if (run == 4) SX_LAUNCH_K1W(4);
-        else if (run == 2) SX_LAUNCH_K1W(2);
-        else SX_LAUNCH_K1W(1);
-#undef SX_LAUNCH_K1W
+        launch_score_columns_lw(ctx, A, run, sx_csc_swizzle(ctx, A), y, c, x, l, u, gamma, s_d, code);
         SX_HIP(hipGetLastError());
         return SX_OK;
     }
@@ -687,20 +595,16 @@ SX_API int sx_score_columns_dev(sx_ctx *ctx, const sx_matrix *A, const double *y
         if (S) {
             SX_TRY(slab_passes(ctx, S, y));
             const sx_slab &L = S->slab[S->R - 1];
-            hipLaunchKernelGGL((k_score_columns<4096, 2>), dim3(walk_grid(ctx, L.ntiles)), dim3(SX_WG), 0, ctx->stream, L.tiles,
+            hipLaunchKernelGGL(k_score_columns<2>, dim3(walk_grid(ctx, L.ntiles)), dim3(SX_WG), 0, ctx->stream, L.tiles,
                                L.ntiles, ctx->opt_xcd_swizzle, L.ptr, L.idx, L.val, y + L.off, c, x, l, u, gamma, s_d, code,
                                S->carry);
             SX_HIP(hipGetLastError());
             return SX_OK;
         }
     }
-    const unsigned grid = walk_grid(ctx, A->n_csc_tiles);
-#define SX_LAUNCH_K1(CH, NTV)                                                                      \
-    hipLaunchKernelGGL((k_score_columns<CH, NTV>), dim3(grid), dim3(SX_WG), 0, ctx->stream,        \
-                       A->csc_tiles, A->n_csc_tiles, sx_csc_swizzle(ctx, A), A->csc_ptr, A->csc_idx, \
-                       A->csc_val, y, c, x, l, u, gamma, s_d, code, static_cast<const double *>(nullptr))
-    SX_DISPATCH_VARIANT(ctx, SX_LAUNCH_K1);
-#undef SX_LAUNCH_K1
+    hipLaunchKernelGGL(k_score_columns<0>, dim3(walk_grid(ctx, A->n_csc_tiles)), dim3(SX_WG), 0, ctx->stream, A->csc_tiles,
+                       A->n_csc_tiles, sx_csc_swizzle(ctx, A), A->csc_ptr, A->csc_idx, A->csc_val, y, c, x, l, u, gamma, s_d, code,
+                       static_cast<const double *>(nullptr));
     SX_HIP(hipGetLastError());
     return SX_OK;
 }
@@ -725,7 +629,7 @@ SX_API int sx_score_rows_dev(sx_ctx *ctx, const sx_matrix *A, const double *x, c
         if (S) {
             SX_TRY(slab_passes(ctx, S, x));
             const sx_slab &L = S->slab[S->R - 1];
-            hipLaunchKernelGGL((k_score_rows<4096, 2>), dim3(walk_grid(ctx, L.ntiles)), dim3(SX_WG), 0, ctx->stream, L.tiles,
+            hipLaunchKernelGGL(k_score_rows<2>, dim3(walk_grid(ctx, L.ntiles)), dim3(SX_WG), 0, ctx->stream, L.tiles,
                                L.ntiles, ctx->opt_xcd_swizzle, L.ptr, L.idx, L.val, x + L.off, b, y, gamma_dual, s_p, flag,
                                S->carry);
             SX_HIP(hipGetLastError());
@@ -734,13 +638,9 @@ SX_API int sx_score_rows_dev(sx_ctx *ctx, const sx_matrix *A, const double *x, c
     }
     // (linking rows that sit together would all queue on one XCD under the contiguous map: sx_build_tiles)
     const int swz2 = (ctx->opt_xcd_swizzle && A->csr_imbalance <= SX_SWIZZLE_MAX_IMBALANCE) ? 1 : 0;
-    const unsigned grid = swz2 ? walk_grid(ctx, A->n_csr_tiles) : static_cast<unsigned>(A->n_csr_tiles);
-#define SX_LAUNCH_K2(CH, NTV)                                                                      \
-    hipLaunchKernelGGL((k_score_rows<CH, NTV>), dim3(grid), dim3(SX_WG), 0, ctx->stream,           \
-                       A->csr_tiles, A->n_csr_tiles, swz2, A->csr_ptr, A->csr_idx,                 \
-                       A->csr_val, x, b, y, gamma_dual, s_p, flag, static_cast<const double *>(nullptr))
-    SX_DISPATCH_VARIANT(ctx, SX_LAUNCH_K2);
-#undef SX_LAUNCH_K2
+    hipLaunchKernelGGL(k_score_rows<0>, dim3(sx_xcd_grid(A->n_csr_tiles, swz2)), dim3(SX_WG), 0, ctx->stream, A->csr_tiles,
+                       A->n_csr_tiles, swz2, A->csr_ptr, A->csr_idx, A->csr_val, x, b, y, gamma_dual, s_p, flag,
+                       static_cast<const double *>(nullptr));
     SX_HIP(hipGetLastError());
     return SX_OK;
 }
@@ -817,87 +717,46 @@ SX_API int sx_price_dev(sx_ctx *ctx, const sx_matrix *A, const double *y, const 
     SX_REQUIRE(A->ctx->device == ctx->device, "matrix lives on another device");
     SX_REQUIRE(A->csc_ptr != nullptr, "matrix has no CSC layout (row shard?)");
     SX_REQUIRE(y && c && result_dev, "y, c or result is NULL");
-    // the swizzled walk needs a grid that is a multiple of 8 (one slice per XCD)
     SX_TRY(window_autotune(ctx, A, [&](int windowed, int swz_) -> int {
-        int nb_ = static_cast<int>(A->n_csc_tiles < PRICE_GRID ? A->n_csc_tiles : PRICE_GRID) & ~7;
-        if (nb_ < 8) return SX_OK;
-        SX_TRY(sx_reserve(ctx, static_cast<size_t>(nb_) * sizeof(PricePartial)));
-        PricePartial *part_ = static_cast<PricePartial *>(ctx->ws);
-        if (windowed)
-            hipLaunchKernelGGL((k_price_lw<4, 0>), dim3(nb_), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles, swz_, A->csc_win_lo, A->csc_ptr,
-                               A->csc_idx, A->csc_val, A->m, y, c, vbasis, tol, rc, part_);
-        else
-            hipLaunchKernelGGL((k_price<4096, 0>), dim3(nb_), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles, swz_, A->csc_ptr, A->csc_idx,
-                               A->csc_val, y, c, vbasis, tol, rc, part_, static_cast<const double *>(nullptr));
-        return SX_OK;
+        return price_launch(ctx, A->n_csc_tiles, 1, nullptr, [&](int nb, PricePartial *partial) {
+            if (windowed)
+                launch_price_lw(ctx, A, 4, swz_, nb, y, c, vbasis, tol, rc, partial);
+            else
+                hipLaunchKernelGGL(k_price<0>, dim3(nb), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles, swz_, A->csc_ptr,
+                                   A->csc_idx, A->csc_val, y, c, vbasis, tol, rc, partial, static_cast<const double *>(nullptr));
+        });
     }));
-    const int swz = sx_csc_swizzle(ctx, A);
-    int nb = static_cast<int>(A->n_csc_tiles < PRICE_GRID ? A->n_csc_tiles : PRICE_GRID);
-    if (swz) nb &= ~7;
-    if (nb == 0) {
+    if (A->n_csc_tiles == 0) {
         sx_price_result empty = {NAN, -1, 0};
         SX_HIP(hipMemcpyAsync(result_dev, &empty, sizeof(empty), hipMemcpyHostToDevice, ctx->stream));
         SX_HIP(hipStreamSynchronize(ctx->stream));
         return SX_OK;
     }
-    SX_TRY(sx_reserve(ctx, static_cast<size_t>(nb) * sizeof(PricePartial)));
-    PricePartial *partial = static_cast<PricePartial *>(ctx->ws);
+    const int swz = sx_csc_swizzle(ctx, A);
     int run = 0;
     SX_TRY(sx_window_run_csc(ctx, A, &run));
-    if (run) {
-#define SX_LAUNCH_K10W(R)                                                                          \
-    do {                                                                                           \
-        if (ctx->opt_run_prefetch)                                                                 \
-            hipLaunchKernelGGL((k_price_lw<R, 1>), dim3(nb), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, \
-                               A->n_csc_tiles, swz, A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, \
-                               A->m, y, c, vbasis, tol, rc, partial);                              \
-        else                                                                                       \
-            hipLaunchKernelGGL((k_price_lw<R, 0>), dim3(nb), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, \
-                               A->n_csc_tiles, swz, A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, \
-                               A->m, y, c, vbasis, tol, rc, partial);                              \
-    } while (0)
-        if (run == 8) SX_LAUNCH_K10W(8);
-        else if (run == 4) SX_LAUNCH_K10W(4);
-        else if (run == 2) SX_LAUNCH_K10W(2);
-        else SX_LAUNCH_K10W(1);
-#undef SX_LAUNCH_K10W
-        hipLaunchKernelGGL(k_price_final, dim3(1), dim3(SX_WG), 0, ctx->stream, partial,
-                           static_cast<int64_t>(nb), result_dev);
-        SX_HIP(hipGetLastError());
-        return SX_OK;
-    }
+    if (run)
+        return price_launch(ctx, A->n_csc_tiles, swz, result_dev, [&](int nb, PricePartial *partial) {
+            launch_price_lw(ctx, A, run, swz, nb, y, c, vbasis, tol, rc, partial);
+        });
     {   // no locality and an operand beyond L2: slab after slab (sx_slabs.h), pricing in the last pass
         const sx_slabs *S = nullptr;
         SX_TRY(sx_slabs_get(ctx, A, 1, &S));
-        // (a first call builds the slabs with scans in the context's workspace, which may have moved it)
-        SX_TRY(sx_reserve(ctx, static_cast<size_t>(nb > 0 ? nb : 1) * sizeof(PricePartial)));
-        partial = static_cast<PricePartial *>(ctx->ws);
         if (S) {
             SX_TRY(slab_passes(ctx, S, y));
             const sx_slab &L = S->slab[S->R - 1];
             const int swl = (ctx->opt_xcd_swizzle && L.ntiles >= 64) ? 1 : 0;
-            int nbl = static_cast<int>(L.ntiles < PRICE_GRID ? L.ntiles : PRICE_GRID);
-            if (swl) nbl &= ~7;
-            if (nbl < 1) nbl = 1;
-            SX_TRY(sx_reserve(ctx, static_cast<size_t>(nbl) * sizeof(PricePartial)));
-            partial = static_cast<PricePartial *>(ctx->ws);
-            hipLaunchKernelGGL((k_price<4096, 2>), dim3(nbl), dim3(SX_WG), 0, ctx->stream, L.tiles, L.ntiles, swl, L.ptr, L.idx,
-                               L.val, y + L.off, c, vbasis, tol, rc, partial, S->carry);
-            hipLaunchKernelGGL(k_price_final, dim3(1), dim3(SX_WG), 0, ctx->stream, partial, static_cast<int64_t>(nbl), result_dev);
-            SX_HIP(hipGetLastError());
-            return SX_OK;
+            return price_launch(ctx, L.ntiles, swl, result_dev, [&](int nb, PricePartial *partial) {
+                hipLaunchKernelGGL(k_price<2>, dim3(nb), dim3(SX_WG), 0, ctx->stream, L.tiles, L.ntiles, swl, L.ptr, L.idx, L.val,
+                                   y + L.off, c, vbasis, tol, rc, partial, S->carry);
+            });
         }
     }
-#define SX_LAUNCH_K10(CH, NTV)                                                                     \
-    hipLaunchKernelGGL((k_price<CH, NTV>), dim3(nb), dim3(SX_WG), 0, ctx->stream, A->csc_tiles,    \
-                       A->n_csc_tiles, swz, A->csc_ptr, A->csc_idx, A->csc_val, y, c, vbasis, tol, \
-                       rc, partial, static_cast<const double *>(nullptr))
-    SX_DISPATCH_VARIANT(ctx, SX_LAUNCH_K10);
-#undef SX_LAUNCH_K10
-    hipLaunchKernelGGL(k_price_final, dim3(1), dim3(SX_WG), 0, ctx->stream, partial,
-                       static_cast<int64_t>(nb), result_dev);
-    SX_HIP(hipGetLastError());
-    return SX_OK;
+    // (the workspace is reserved here, behind the first call's slab build, whose scans may have moved it)
+    return price_launch(ctx, A->n_csc_tiles, swz, result_dev, [&](int nb, PricePartial *partial) {
+        hipLaunchKernelGGL(k_price<0>, dim3(nb), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles, swz, A->csc_ptr,
+                           A->csc_idx, A->csc_val, y, c, vbasis, tol, rc, partial, static_cast<const double *>(nullptr));
+    });
 }
 
 // ------------------------------------------------------------------ host-pointer wrappers

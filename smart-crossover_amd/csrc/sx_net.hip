@@ -215,8 +215,7 @@ SX_API int sx_flow_indicator_mcf_dev(sx_ctx *ctx, const sx_matrix *A, const doub
     hipLaunchKernelGGL(k_mcf_xhat, dim3(grid1d(E)), dim3(SX_WG), 0, s, E, x, u, xhat, mask);
     if (V > 0) {
         const int swz = ctx->opt_xcd_swizzle;
-        const unsigned grid = swz ? static_cast<unsigned>(((A->n_csr_tiles + 7) >> 3) << 3)
-                                  : static_cast<unsigned>(A->n_csr_tiles);
+        const unsigned grid = sx_xcd_grid(A->n_csr_tiles, swz);
         hipLaunchKernelGGL(k_mcf_throughput, dim3(grid), dim3(SX_WG), 0, s, A->csr_tiles, A->n_csr_tiles, swz,
                            A->csr_ptr, A->csr_idx, A->csr_val, xhat, mask, f_inv, f_out);
     }
@@ -248,8 +247,7 @@ SX_API int sx_mcf_node_flows_dev(sx_ctx *ctx, const sx_matrix *A_rows, const dou
     SX_REQUIRE(A_rows->csr_ptr != nullptr, "the node block needs the row layout");
     if (A_rows->m == 0) return SX_OK;
     const int swz = ctx->opt_xcd_swizzle;
-    const unsigned grid = swz ? static_cast<unsigned>(((A_rows->n_csr_tiles + 7) >> 3) << 3)
-                              : static_cast<unsigned>(A_rows->n_csr_tiles);
+    const unsigned grid = sx_xcd_grid(A_rows->n_csr_tiles, swz);
     hipLaunchKernelGGL(k_mcf_throughput, dim3(grid), dim3(SX_WG), 0, ctx->stream, A_rows->csr_tiles, A_rows->n_csr_tiles,
                        swz, A_rows->csr_ptr, A_rows->csr_idx, A_rows->csr_val, xhat_all, mask_all, f_inv, f_out);
     SX_HIP(hipGetLastError());

@@ -92,7 +92,7 @@ int check_matrix(const sx_ctx *ctx, const sx_matrix *A) {
 int launch_walk(sx_ctx *ctx, const sx_matrix *A, const double *x, const double *l, const double *u, int numerator,
                 double *sumsq, double *norm, double *score) {
     const int swz = (ctx->opt_xcd_swizzle && A->n_csc_tiles >= 64) ? 1 : 0;
-    const unsigned grid = static_cast<unsigned>(swz ? ((A->n_csc_tiles + 7) >> 3) << 3 : A->n_csc_tiles);
+    const unsigned grid = sx_xcd_grid(A->n_csc_tiles, swz);
     hipLaunchKernelGGL(k_column_norms, dim3(grid), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles, swz,
                        A->csc_ptr, A->csc_val, x, l, u, numerator, sumsq, norm, score);
     SX_HIP(hipGetLastError());

@@ -387,14 +387,8 @@ __global__ __launch_bounds__(RB_TW, RB_MINW) void k_rb_cg_a(RbLayout L, int swiz
     if (st->done) return;
     __shared__ RbLds lds;
     __shared__ double wave_sum[RB_TW / 64];
-    int64_t t = blockIdx.x, t_end = L.nst, t_step = gridDim.x;
-    if (swizzle) { // gridDim.x is a multiple of 8: XCD k walks the contiguous super-tiles [k*per, (k+1)*per)
-        const int64_t per = (L.nst + 7) >> 3;
-        t = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        t_end = ((blockIdx.x & 7) + 1) * per;
-        if (t_end > L.nst) t_end = L.nst;
-        t_step = gridDim.x >> 3;
-    }
+    int64_t t, t_end, t_step;
+    sx_walk_range(L.nst, swizzle, t, t_end, t_step);
     double dot = 0.0;
     if (order) { // slots of the dealt map: a block keeps to the slots of its XCD (gridDim.x is a multiple of 8)
         t = blockIdx.x;
@@ -462,9 +456,8 @@ __global__ __launch_bounds__(RB_LP_WG, RB_LP_MINW) void k_rb_long_products(int64
     if (st && st->done) return;
     __shared__ double piece_prod[RB_PIECE];
     const int64_t npieces = (nl + RB_PIECE - 1) / RB_PIECE;
-    const int64_t per = (npieces + 7) >> 3;
-    const int64_t piece = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if ((blockIdx.x >> 3) >= per || piece >= npieces) return;
+    const int64_t piece = sx_tile_of_block(blockIdx.x, npieces, 1);
+    if (piece >= npieces) return;
     const int64_t i0 = piece * RB_PIECE;
     const int cnt = static_cast<int>(nl - i0 < RB_PIECE ? nl - i0 : RB_PIECE);
     const uint32_t cnt4 = static_cast<uint32_t>((cnt + 3) & ~3); // the lists hold 8 zeroed entries behind the last one
@@ -506,7 +499,7 @@ __global__ __launch_bounds__(RB_LP_WG, RB_LP_MINW) void k_rb_long_products(int64
 
 inline int rb_long_products(sx_ctx *ctx, const sx_rowblock *rb, const double *x, const RbCgState *st) {
     const int64_t npieces = (rb->nl + RB_PIECE - 1) / RB_PIECE;
-    hipLaunchKernelGGL(k_rb_long_products, dim3(static_cast<unsigned>(((npieces + 7) >> 3) << 3)), dim3(RB_LP_WG), 0, ctx->stream,
+    hipLaunchKernelGGL(k_rb_long_products, dim3(sx_xcd_grid(npieces, 1)), dim3(RB_LP_WG), 0, ctx->stream,
                        rb->nl, rb->lcol, rb->lval, rb->lperm, x, rb->lprod, st);
     return SX_OK;
 }
@@ -594,7 +587,7 @@ int sx_rb_score_rows(sx_ctx *ctx, const sx_rowblock *rb, int64_t ncols, const do
                      const double *y, double gamma_dual, double *s_p, uint8_t *flag) {
     if (rb->nst == 0) return SX_OK;
     const int swz = ctx->opt_xcd_swizzle;
-    unsigned grid = swz ? static_cast<unsigned>(((rb->nst + 7) >> 3) << 3) : static_cast<unsigned>(rb->nst);
+    unsigned grid = sx_xcd_grid(rb->nst, swz);
     const int32_t *order = rb_order(ctx, rb);
     if (order) grid = static_cast<unsigned>(rb->order_n);
     if (rb->nl > 0) SX_TRY(rb_long_products(ctx, rb, x, nullptr));

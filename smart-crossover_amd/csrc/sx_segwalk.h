@@ -41,16 +41,30 @@ __device__ __forceinline__ int64_t sx_tile_of_block(int64_t b, int64_t ntiles, i
     return t; // may be >= ntiles for the last XCD's tail: caller skips
 }
 
+// The same map for a grid-stride walk over n items: this workgroup visits t, t + t_step, ... below t_end.  With the
+// map on (gridDim.x is a multiple of 8) XCD k = blockIdx % 8 walks the contiguous range [k*per, (k+1)*per) with its
+// gridDim/8 blocks.
+__device__ __forceinline__ void sx_walk_range(int64_t n, int swizzle, int64_t &t, int64_t &t_end, int64_t &t_step) {
+    t = blockIdx.x;
+    t_end = n;
+    t_step = gridDim.x;
+    if (swizzle) {
+        const int64_t per = (n + 7) >> 3;
+        t = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+        t_end = ((blockIdx.x & 7) + 1) * per;
+        if (t_end > n) t_end = n;
+        t_step = gridDim.x >> 3;
+    }
+}
+
 typedef int sx_v4i __attribute__((ext_vector_type(4)));
 typedef double sx_v2d __attribute__((ext_vector_type(2)));
 
 // 16-byte loads of the streamed entry arrays.  NT selects how they are issued:
 //   0        plain global loads;
-//   1        global loads marked non-temporal;
-//   >= 2     raw buffer loads whose cache-policy bits are NT (2 = nt, 16 = sc1, 17 = sc0 sc1,
-//            18 = nt sc1): the once-read stream is fetched at agent scope so that it does not
-//            displace the gathered operand from the 32 KB vector L1.  The descriptor is rebased
-//            to the chunk, so the 32-bit byte offsets never leave the chunk.
+//   2        raw buffer loads whose cache-policy bits are NT (the slab passes, sx_slabs.h): the once-read stream is
+//            fetched at agent scope so that it does not displace the gathered operand from the 32 KB vector L1.  The
+//            descriptor is rebased to the chunk, so the 32-bit byte offsets never leave the chunk.
 struct sx_stream {
     const int32_t *idx;
     const double *val;
@@ -59,10 +73,11 @@ struct sx_stream {
 
 template <int NT>
 __device__ __forceinline__ sx_stream sx_stream_at(const int32_t *idx, const double *val, int64_t base) {
+    static_assert(NT == 0 || NT == 2, "stream policy: 0 (plain) or 2 (nt buffer loads)");
     sx_stream s;
     s.idx = idx + base;
     s.val = val + base;
-    if constexpr (NT >= 2) {
+    if constexpr (NT == 2) {
         s.ridx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(s.idx), 0, 0x7fffffff, 0x00020000);
         s.rval = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(s.val), 0, 0x7fffffff, 0x00020000);
     }
@@ -72,16 +87,12 @@ __device__ __forceinline__ sx_stream sx_stream_at(const int32_t *idx, const doub
 // entries [off, off+4) of the chunk
 template <int NT>
 __device__ __forceinline__ void sx_ld_quad(const sx_stream &s, int off, sx_v4i &i4, sx_v2d &v01, sx_v2d &v23) {
-    if constexpr (NT >= 2) {
+    if constexpr (NT == 2) {
         i4 = __builtin_amdgcn_raw_buffer_load_b128(s.ridx, off * 4, 0, NT);
         const sx_v4i a = __builtin_amdgcn_raw_buffer_load_b128(s.rval, off * 8, 0, NT);
         const sx_v4i b = __builtin_amdgcn_raw_buffer_load_b128(s.rval, off * 8 + 16, 0, NT);
         v01 = __builtin_bit_cast(sx_v2d, a);
         v23 = __builtin_bit_cast(sx_v2d, b);
-    } else if constexpr (NT == 1) {
-        i4 = __builtin_nontemporal_load(reinterpret_cast<const sx_v4i *>(s.idx + off));
-        v01 = __builtin_nontemporal_load(reinterpret_cast<const sx_v2d *>(s.val + off));
-        v23 = __builtin_nontemporal_load(reinterpret_cast<const sx_v2d *>(s.val + off + 2));
     } else {
         i4 = *reinterpret_cast<const sx_v4i *>(s.idx + off);
         v01 = *reinterpret_cast<const sx_v2d *>(s.val + off);
@@ -89,16 +100,68 @@ __device__ __forceinline__ void sx_ld_quad(const sx_stream &s, int off, sx_v4i &
     }
 }
 
-// Stage functor:  void operator()(double value, int32_t index, double (&out)[NACC]) const
-// Walks tile `tile` (segments [tiles[tile], tiles[tile+1])).  On return acc[] holds the NACC
-// running sums of segment `seg` (valid lanes only).
 struct sx_no_prologue {
     __device__ __forceinline__ void operator()(int64_t, bool) const {}
+};
+
+// What a lane knows about its tile: its segment (valid when the tile has that many), the segment's entries [cs, ce)
+// (empty for the other lanes) and the tile's slice [p_lo, p_hi) of the entry arrays.
+struct sx_lane {
+    int64_t seg, cs, ce, p_lo, p_hi;
+    bool valid;
 };
 
 // `pre(seg, valid)` runs as soon as the lane knows its segment, before any entry is streamed: the
 // place to issue the loads an epilogue will need (c, x, l, u ...) so that their HBM latency overlaps
 // the walk instead of following it.
+template <class Pre>
+__device__ __forceinline__ sx_lane sx_walk_lane(const int64_t *__restrict__ tiles, int64_t tile,
+                                                const int64_t *__restrict__ ptr, const Pre &pre) {
+    sx_lane L;
+    const int64_t s0 = tiles[tile];
+    const int64_t s1 = tiles[tile + 1];
+    L.seg = s0 + threadIdx.x;
+    L.valid = L.seg < s1;
+    pre(L.seg, L.valid);
+    L.p_lo = ptr[s0];
+    L.p_hi = ptr[s1];
+    L.cs = L.ce = L.p_hi;
+    if (L.valid) {
+        L.cs = ptr[L.seg];
+        L.ce = ptr[L.seg + 1];
+    }
+    return L;
+}
+
+// consume: the lane's entries inside the staged chunk [base, base + CHUNK), strictly sequential, the LDS reads
+// batched eight ahead of the dependent adds
+template <int NACC, int CHUNK>
+__device__ __forceinline__ void sx_consume(const sx_walk_lds<NACC, CHUNK> &lds, const sx_lane &L, int64_t base,
+                                           double (&acc)[NACC]) {
+    const int64_t k0 = L.cs > base ? L.cs : base;
+    const int64_t k1 = L.ce < base + CHUNK ? L.ce : base + CHUNK;
+    int o = static_cast<int>(k0 - base);
+    int left = (k1 > k0) ? static_cast<int>(k1 - k0) : 0;
+    for (; left >= 8; left -= 8, o += 8) {
+        double t[NACC][8];
+#pragma unroll
+        for (int a = 0; a < NACC; ++a)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) t[a][q] = lds.v[a][o + q];
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+#pragma unroll
+            for (int a = 0; a < NACC; ++a) acc[a] = acc[a] + t[a][q];
+    }
+    for (; left > 0; --left, ++o) {
+#pragma unroll
+        for (int a = 0; a < NACC; ++a) acc[a] = acc[a] + lds.v[a][o];
+    }
+}
+
+// Stage functor:  void operator()(double value, int32_t index, double (&out)[NACC]) const
+// Walks tile `tile` (segments [tiles[tile], tiles[tile+1])).  On return acc[] holds the NACC
+// running sums of segment `seg` (valid lanes only).
 template <int NACC, int CHUNK, int NT = 0, class Stage, class Pre = sx_no_prologue>
 __device__ __forceinline__ void sx_segwalk(const int64_t *__restrict__ tiles, int64_t tile,
                                            const int64_t *__restrict__ ptr,
@@ -107,24 +170,16 @@ __device__ __forceinline__ void sx_segwalk(const int64_t *__restrict__ tiles, in
                                            sx_walk_lds<NACC, CHUNK> &lds, int64_t &seg, bool &valid,
                                            double (&acc)[NACC], const Pre &pre = Pre(), const bool keep = false) {
     const int tid = threadIdx.x;
-    const int64_t s0 = tiles[tile];
-    const int64_t s1 = tiles[tile + 1];
-    seg = s0 + tid;
-    valid = seg < s1;
-    pre(seg, valid);
-    const int64_t p_lo = ptr[s0];
-    const int64_t p_hi = ptr[s1];
-    int64_t cs = p_hi, ce = p_hi;
-    if (valid) {
-        cs = ptr[seg];
-        ce = ptr[seg + 1];
-    }
+    const sx_lane L = sx_walk_lane(tiles, tile, ptr, pre);
+    seg = L.seg;
+    valid = L.valid;
+    const int64_t p_hi = L.p_hi;
     if (!keep) { // keep: the sums continue from what the caller (or its `pre`) left in acc[] -- sx_slabs.h
 #pragma unroll
         for (int a = 0; a < NACC; ++a) acc[a] = 0.0;
     }
 
-    for (int64_t base = p_lo & ~static_cast<int64_t>(3); base < p_hi; base += CHUNK) {
+    for (int64_t base = L.p_lo & ~static_cast<int64_t>(3); base < p_hi; base += CHUNK) {
         // ---- stage: CHUNK / SX_SWEEP sweeps of 1024 entries
         const sx_stream src = sx_stream_at<NT>(idx, val, base);
 #pragma unroll
@@ -153,26 +208,7 @@ __device__ __forceinline__ void sx_segwalk(const int64_t *__restrict__ tiles, in
             }
         }
         __syncthreads();
-        // ---- consume: strictly sequential per lane, reads batched ahead of the adds
-        const int64_t k0 = cs > base ? cs : base;
-        const int64_t k1 = ce < base + CHUNK ? ce : base + CHUNK;
-        int o = static_cast<int>(k0 - base);
-        int left = (k1 > k0) ? static_cast<int>(k1 - k0) : 0;
-        for (; left >= 8; left -= 8, o += 8) {
-            double t[NACC][8];
-#pragma unroll
-            for (int a = 0; a < NACC; ++a)
-#pragma unroll
-                for (int q = 0; q < 8; ++q) t[a][q] = lds.v[a][o + q];
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-#pragma unroll
-                for (int a = 0; a < NACC; ++a) acc[a] = acc[a] + t[a][q];
-        }
-        for (; left > 0; --left, ++o) {
-#pragma unroll
-            for (int a = 0; a < NACC; ++a) acc[a] = acc[a] + lds.v[a][o];
-        }
+        sx_consume(lds, L, base, acc);
         __syncthreads();
     }
 }

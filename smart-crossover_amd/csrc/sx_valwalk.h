@@ -18,22 +18,14 @@ __device__ __forceinline__ void sx_valwalk(const int64_t *__restrict__ tiles, in
                                            const Stage &stage, sx_walk_lds<1, CHUNK> &lds, int64_t &seg,
                                            bool &valid, double &acc, const Pre &pre = Pre()) {
     const int tid = threadIdx.x;
-    const int64_t s0 = tiles[tile];
-    const int64_t s1 = tiles[tile + 1];
-    seg = s0 + tid;
-    valid = seg < s1;
-    pre(seg, valid);
-    const int64_t p_lo = ptr[s0];
-    const int64_t p_hi = ptr[s1];
-    int64_t cs = p_hi, ce = p_hi;
-    if (valid) {
-        cs = ptr[seg];
-        ce = ptr[seg + 1];
-    }
-    acc = 0.0;
+    const sx_lane L = sx_walk_lane(tiles, tile, ptr, pre);
+    seg = L.seg;
+    valid = L.valid;
+    const int64_t p_hi = L.p_hi;
+    double sum[1] = {0.0};
 
     // two doubles per load: the stream starts on an even entry, so that every load is 16-byte aligned
-    for (int64_t base = p_lo & ~static_cast<int64_t>(1); base < p_hi; base += CHUNK) {
+    for (int64_t base = L.p_lo & ~static_cast<int64_t>(1); base < p_hi; base += CHUNK) {
         const double *__restrict__ src = val + base;
 #pragma unroll
         for (int r = 0; r < CHUNK / SX_SWEEP; ++r) {
@@ -52,19 +44,8 @@ __device__ __forceinline__ void sx_valwalk(const int64_t *__restrict__ tiles, in
             }
         }
         __syncthreads();
-        // ---- consume: strictly sequential per lane, reads batched ahead of the adds
-        const int64_t k0 = cs > base ? cs : base;
-        const int64_t k1 = ce < base + CHUNK ? ce : base + CHUNK;
-        int o = static_cast<int>(k0 - base);
-        int left = (k1 > k0) ? static_cast<int>(k1 - k0) : 0;
-        for (; left >= 8; left -= 8, o += 8) {
-            double t[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) t[q] = lds.v[0][o + q];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc = acc + t[q];
-        }
-        for (; left > 0; --left, ++o) acc = acc + lds.v[0][o];
+        sx_consume(lds, L, base, sum);
         __syncthreads();
     }
+    acc = sum[0];
 }

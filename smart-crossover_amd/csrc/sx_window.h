@@ -12,6 +12,8 @@
 
 #include "sx_segwalk.h"
 
+#include <type_traits>
+
 #ifndef SXL_CAP_V
 #define SXL_CAP_V 4096
 #endif
@@ -41,4 +43,41 @@ __device__ __forceinline__ void sx_window_fill(double *win, const double *__rest
         if (row > bound - 1) row = bound - 1;
         win[k] = vec[row];
     }
+}
+
+// One run of a windowed walk: tiles [run * RUN, +RUN) of `tiles` behind the window of the run's middle tile.  All lanes
+// of the workgroup call it; `reuse`: the workgroup has walked a run before (a kernel with one run per workgroup spares
+// the first barrier).  `epi` is the calling kernel's epilogue object: load(seg, valid) requests its operands of a segment
+// as soon as the lane knows it (they fly under the walk), finish(seg, sum) completes a valid segment from its sum.  The
+// sums start from +0.0 and are those of the plain walk: the window only changes where an operand is read from.
+template <int RUN, class Epi>
+__device__ __forceinline__ void sx_window_walk(const int64_t *__restrict__ tiles, int64_t ntiles, int64_t run,
+                                               const int32_t *__restrict__ win_lo, const int64_t *__restrict__ ptr,
+                                               const int32_t *__restrict__ idx, const double *__restrict__ val,
+                                               const double *__restrict__ vec, int64_t bound,
+                                               sx_walk_lds<1, SXL_CHUNK> &lds, double *win, const bool reuse,
+                                               Epi &epi) {
+    const int64_t t0 = run * RUN;
+    const int64_t t1 = (t0 + RUN < ntiles) ? t0 + RUN : ntiles;
+    const int64_t wlo = win_lo[(t0 + t1 - 1) >> 1];
+    if (reuse) __syncthreads(); // the previous run's gathers are done with the window
+    sx_window_fill(win, vec, wlo, bound);
+    __syncthreads();
+    for (int64_t t = t0; t < t1; ++t) {
+        double acc[1];
+        int64_t seg;
+        bool valid;
+        auto pre = [&](int64_t sg, bool ok) { epi.load(sg, ok); };
+        sx_segwalk<1, SXL_CHUNK>(tiles, t, ptr, idx, val, sx_stage_win{vec, win, wlo}, lds, seg, valid, acc, pre);
+        if (valid) epi.finish(seg, acc[0]);
+    }
+}
+
+// Host side: launch(std::integral_constant<int, R>) for the first R of the list that `run` (tiles per window load,
+// sx_window_run_csc) reaches, the last R of the list otherwise: the instantiations a windowed kernel is built for.
+template <int R, int... REST, class Launch>
+inline void sx_window_with_run(int run, const Launch &launch) {
+    if constexpr (sizeof...(REST) == 0) launch(std::integral_constant<int, R>{});
+    else if (run >= R) launch(std::integral_constant<int, R>{});
+    else sx_window_with_run<REST...>(run, launch);
 }

@@ -93,6 +93,34 @@ def test_projector_graph_replay_equals_direct_launches(ctx):
     assert out[(1, 50)][1] == 50 and out[(1, 7)][1] == 7 and out[(1, 1000)][2] == 1
 
 
+def test_projector_window_option_never_changes_results(ctx):
+    """The column pass of the CG behind the LDS operand window (1 / 4 / 8 tiles per load) against the plain
+    one (0): the window only changes where an operand is read from, so every iterate -- hence the
+    iteration count, the norm and the projection itself -- is the same bit for bit.  79 column tiles:
+    the XCD map is on (>= 64) and the last run of 4 is partial."""
+    A = sp.csr_matrix(workloads.lp_shard(0, 1, m=6000, n_block=20000, k=8, structure="staircase", window=300).col_block)
+    m, n = A.shape
+    xa = np.random.default_rng(21).uniform(0.1, 1, n)
+    xs = np.random.default_rng(22).uniform(0.1, 1, m)
+    c = np.random.default_rng(23).standard_normal(n)
+    dA = ctx.matrix(A)
+    d_xa, d_xs, d_c = ctx.to_device(xa), ctx.to_device(xs), ctx.to_device(c)
+    out = {}
+    try:
+        for window in (0, 1, 4, 8):
+            ctx.set_option("window", window)
+            pc = ctx.empty(n, np.float64)
+            r = ctx.projector_norm(dA, d_xa, d_xs, d_c, 1e-14, 20, pc, None)
+            out[window] = ((r.proj_norm, int(r.iters), int(r.converged), r.rel_residual), pc.download())
+    finally:
+        ctx.set_option("window", -1)
+        dA.free()
+    assert out[0][0][1] >= 1
+    for window in (1, 4, 8):
+        assert out[window][0] == out[0][0], window
+        assert np.array_equal(out[window][1].view(np.uint64), out[0][1].view(np.uint64)), window
+
+
 def test_projector_config2_size_hits_cap(ctx, capsys):
     """Config 2 (2e4 x 1e5): the reference's CG runs into maxiter=1000 here and its
     result then depends on rounding order; the device must finish, report 1000 iterations and land

@@ -239,6 +239,9 @@ def test_host_pointer_entry_points(ctx):
     # error mapping: NULL matrix -> SX_ERR_INVALID -> ValueError
     with pytest.raises(ValueError):
         sxl.check(lib.sx_score_rows(ctx.handle, None, p(inst.x), p(inst.b), p(inst.y), 1e-3, p(s_p), p(flag)))
+    # the options of the removed walk variants are unknown keys like any other
+    for key in (b"run_prefetch", b"nt_stream", b"chunk", b"no_such_option"):
+        assert lib.sx_ctx_set_option(ctx.handle, key, 0) == sxl.SX_ERR_INVALID, key
 
 
 def test_matrix_index_arrays_are_validated(ctx):
@@ -311,13 +314,18 @@ def test_window_option_never_changes_results(ctx, structure, window):
     sh = workloads.lp_shard(0, 1, m=40_000, n_block=300_000, k=8, structure=structure, window=window)
     A = sh.col_block
     dC = ctx.column_shard(A)
-    n = A.shape[1]
-    d = {k: ctx.to_device(getattr(sh, k)) for k in ("y", "x", "c", "l", "u")}
     want_sd = sh.c - A.T @ sh.y                 # CSR matvec of the transposed view: stored order per column
-    want_code = L.column_codes(sh.x, sh.l, sh.u, want_sd, L.GAMMA0)
+    check_window_settings(ctx, dC, A, {k: getattr(sh, k) for k in ("y", "x", "c", "l", "u")}, want_sd)
+
+
+def check_window_settings(ctx, dC, A, vec, want_sd):
+    """K1 and K10 on the resident matrix dC (= A) under every "window" setting, against the oracle; frees dC."""
+    n = A.shape[1]
+    d = {k: ctx.to_device(v) for k, v in vec.items()}
+    want_code = L.column_codes(vec["x"], vec["l"], vec["u"], want_sd, L.GAMMA0)
     rng = np.random.default_rng(5)
     vb = rng.integers(-2, 1, n).astype(np.int8)
-    want_rc = N.mcf_reduced_cost(A, sh.c, sh.y, vb.astype(int))
+    want_rc = N.mcf_reduced_cost(A, vec["c"], vec["y"], vb.astype(int))
     dvb = ctx.to_device(vb)
     try:
         for opt in (0, 1, 2, 4, 8, -1):
@@ -334,3 +342,14 @@ def test_window_option_never_changes_results(ctx, structure, window):
     finally:
         ctx.set_option("window", -1)
         dC.free()
+
+
+def test_window_option_on_ragged_matrix(ctx):
+    """The same settings on ragged_matrix(): a column of nine 1,024-entry chunks of the windowed walk, empty
+    columns, unsorted indices with duplicates, and fewer tiles than one run of 8."""
+    A = ragged_matrix()
+    m, n = A.shape
+    rng = np.random.default_rng(1)
+    vec = {"y": rng.standard_normal(m), "x": rng.standard_normal(n), "c": rng.standard_normal(n),
+           "l": np.where(rng.random(n) < 0.2, -np.inf, 0.0), "u": np.where(rng.random(n) < 0.5, np.inf, 2.0)}
+    check_window_settings(ctx, ctx.matrix(A), A, vec, L.dual_slack(A, vec["c"], vec["y"]))

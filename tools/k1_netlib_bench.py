@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """K1 / K10 (column walks) on netlib_lp at config-5 size under the walk's knobs: LDS window off / auto / 4 tiles per load,
-XCD map on / off, chunk 4096 / 2048.  MI355X.  usage: python tools/k1_netlib_bench.py"""
+XCD map on / off.  MI355X.  usage: python tools/k1_netlib_bench.py"""
 import itertools
 import os
 import sys
@@ -23,7 +23,7 @@ vb = ctx.to_device(np.where(np.arange(n) % 7 == 0, -2, -1).astype(np.int8))
 s_d, code = ctx.empty(n, np.float64), ctx.empty(n, np.uint8)
 k1_bytes = 12 * inst.A.nnz + 49 * n + 8 * m
 k10_bytes = 12 * inst.A.nnz + 17 * n + 8 * m
-variants = list(itertools.product((1, 0), (-1, 0, 1, 4), (4096, 2048)))
+variants = list(itertools.product((1, 0), (-1, 0, 1, 4)))
 res = {v: {"k1": [], "k10": []} for v in variants}
 ref = None
 pres = None
@@ -31,7 +31,6 @@ for rnd in range(5):
     for v in variants:
         ctx.set_option("xcd_swizzle", v[0])
         ctx.set_option("window", v[1])
-        ctx.set_option("chunk", v[2])
         ctx.score_columns(dA, d["y"], d["c"], d["x"], d["l"], d["u"], 1e-3, s_d, code)
         ctx.marker(0)
         for _ in range(5):
@@ -49,4 +48,4 @@ for rnd in range(5):
         assert np.array_equal(ref, got), v
 for v in variants:
     t1, t10 = np.median(res[v]["k1"]), np.median(res[v]["k10"])
-    print(f"swizzle={v[0]} window={v[1]:2d} chunk={v[2]}: K1 {t1:.4f} ms = {k1_bytes / t1 / 1e6 / 8000:.3f} of peak; K10 {t10:.4f} ms = {k10_bytes / t10 / 1e6 / 8000:.3f}", flush=True)
+    print(f"swizzle={v[0]} window={v[1]:2d}: K1 {t1:.4f} ms = {k1_bytes / t1 / 1e6 / 8000:.3f} of peak; K10 {t10:.4f} ms = {k10_bytes / t10 / 1e6 / 8000:.3f}", flush=True)

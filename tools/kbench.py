@@ -26,7 +26,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=int, default=4096, help="staircase window W (rows) of the synthetic LP")
-    ap.add_argument("--variants", default="all", help="'all' or 'default' (swizzle on, nt off, chunk 4096 only)")
+    ap.add_argument("--variants", default="all", help="'all' (XCD map off / on, plain walk), 'default' (plain / windowed), 'window' or 'slabs'")
     args = ap.parse_args()
     m, nb, k = (1_000_000, 10_000_000, 8) if args.workload == "c5" else (20_000, 100_000, 20)
     structure = args.structure if args.workload == "c5" else "uniform"
@@ -43,29 +43,20 @@ def main():
     rc = ctx.empty(nb, np.float64)
     pres = None
 
-    variants = list(itertools.product((0, 1), (0, 1), (4096, 2048), (0,)))   # swizzle, nt, chunk, lds-window
+    variants = list(itertools.product((0, 1), (0,), (-1,)))   # swizzle, lds-window, slabs
     if args.variants == "default":
-        variants = [(1, 0, 4096, 0), (1, 0, 4096, 1)]
+        variants = [(1, 0, -1), (1, 1, -1)]
     elif args.variants == "window":   # LDS operand window, tiles per workgroup
-        variants = [(1, 0, 4096, w) for w in (0, 1, 4, -1)]
-    elif args.variants == "policy":   # cache policy of the streamed loads (see sx_segwalk.h)
-        variants = [(1, p, 4096, 0) for p in (0, 1, 2, 16, 17, 18)]
-    elif args.variants == "runwalk":  # windowed walk tile by tile (0) / with its loads one step ahead (1), sx_runwalk.h
-        variants = [(1, 0, 4096, -1, pf) for pf in (0, 1)]
+        variants = [(1, w, -1) for w in (0, 1, 4, -1)]
     elif args.variants == "slabs":    # operand slabs of the walks without locality (sx_slabs.h): never / automatic
-        variants = [(1, 0, 4096, -1, 0, sl) for sl in ([0, -1] + [int(q) for q in os.environ.get("SLABS", "").split(",") if q])]
+        variants = [(1, -1, sl) for sl in ([0, -1] + [int(q) for q in os.environ.get("SLABS", "").split(",") if q])]
     res = {v: {"k1": [], "k2": [], "k10": []} for v in variants}
     ref = None
     for rnd in range(args.rounds):
         for v in variants:
             ctx.set_option("xcd_swizzle", v[0])
-            ctx.set_option("nt_stream", v[1])
-            ctx.set_option("chunk", v[2])
-            ctx.set_option("window", v[3])
-            if len(v) > 4:
-                ctx.set_option("run_prefetch", v[4])
-            if len(v) > 5:
-                ctx.set_option("slabs", v[5])
+            ctx.set_option("window", v[1])
+            ctx.set_option("slabs", v[2])
             ctx.score_columns(dC, d["y"], d["c"], d["x"], d["l"], d["u"], 1e-3, s_d, code)   # warm (layouts are built on first use)
             ctx.score_rows(dR, d["x"], d["b"], d["y"], 1e-3, s_p, flag)
             ctx.marker(0)
@@ -90,11 +81,10 @@ def main():
                     ref = got
                 assert got == ref or os.environ.get("SX_KBENCH_NOCHECK"), f"variant {v} changed the results"   # (NOCHECK: phase-stripped library variants)
     print(f"workload {args.workload}/{structure} window={args.window}: K1 bytes {k1_bytes/1e9:.3f} GB, K2 bytes {k2_bytes/1e9:.3f} GB")
-    print("swz nt chunk win |  K1 med ms   min ms   GB/s(med) |  K2 med ms   min ms   GB/s(med) | K10 med ms   min ms   GB/s(med)")
+    print("swz win slabs |  K1 med ms   min ms   GB/s(med) |  K2 med ms   min ms   GB/s(med) | K10 med ms   min ms   GB/s(med)")
     for v in variants:
-        extra = "".join(f"/{q}" for q in v[4:])
         a, b, p10 = np.array(res[v]["k1"]), np.array(res[v]["k2"]), np.array(res[v]["k10"])
-        print(f" {v[0]} {v[1]:2d}  {v[2]:4d} {v[3]:3d}{extra} |  {np.median(a):8.4f} {a.min():8.4f} {k1_bytes/np.median(a)/1e6:9.0f} |"
+        print(f" {v[0]}  {v[1]:3d}  {v[2]:4d}  |  {np.median(a):8.4f} {a.min():8.4f} {k1_bytes/np.median(a)/1e6:9.0f} |"
               f"  {np.median(b):8.4f} {b.min():8.4f} {k2_bytes/np.median(b)/1e6:9.0f} |"
               f"  {np.median(p10):8.4f} {p10.min():8.4f} {k10_bytes/np.median(p10)/1e6:9.0f}")
 
