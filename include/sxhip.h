@@ -552,6 +552,17 @@ int sx_denselu_destroy(sx_denselu *h);
  *                                the reference's warm-started final solve (lp_methods/algorithms.py:69-74,
  *                                lp_manager.py:79-89); a basis with too few / too many members is completed by logicals /
  *                                thinned to superbasic columns; both NULL = sx_crossover_band_dev.
+ * Bounds: l[j] may be -inf and u[j] +inf in any combination.  A NON-BASIC column rests
+ *     l, u finite (a box, l = u: fixed)   at the bound its code names (guessed entry: the nearer one); a fixed column never enters
+ *     l finite, u = +inf                  at l (a code -2 is read as -1)
+ *     l = -inf, u finite                  at u (a code -1 is read as -2)
+ *     l = -inf, u = +inf (free)           at 0, whatever its code
+ * and the basic solution is B x_B = b - A_N x_N with those values.  Pricing: a column at its lower bound may enter with
+ * reduced cost d < -opt_tol, one at its upper bound with d > opt_tol, a free one with |d| > opt_tol (BOTH signs; it moves in
+ * the direction d names and is basic afterwards, or the LP is unbounded: status 2).  On return vbasis[j] is -1 / -2 only at
+ * a FINITE bound, with x[j] equal to that bound bit for bit; a non-basic free column is reported as -3 (the code it
+ * is read with) with x[j] = 0.0 -- unless it STARTED superbasic away from 0 and prices at 0 within opt_tol: no bound to be
+ * pushed to, it keeps its value --, and -3 appears on no column that has a bound when the status is 0.
  * Return SX_ERR_UNSUPPORTED when the matched basis is no band matrix the band LU takes (kl + 32 <= 1536 and
  * kl + ku + 32 <= 1980) or its border passes 16,384 rows (the caller then takes sx_simplex_crossover_dev).  Outputs and
  * result as sx_simplex_crossover_dev; result->phase1_iters counts the columns pricing added to the tableau,

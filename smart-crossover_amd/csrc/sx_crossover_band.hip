@@ -2192,7 +2192,9 @@ int crossover_band_impl(sx_ctx *ctx, const sx_matrix *A, const double *b, const 
             for (int64_t j = 0; j < n; ++j) {
                 if (vstat[j] != 0 || hl[j] == hu[j]) continue;
                 const double d = hrc[j];
-                if (atup[j] ? d > opt_tol : d < -opt_tol) viol.emplace_back(std::fabs(d), static_cast<int32_t>(j));
+                // a free column rests at 0 and may move either way (it loads as TB_SUP): both signs price
+                const bool free_col = std::isinf(hl[j]) && std::isinf(hu[j]);
+                if (free_col ? std::fabs(d) > opt_tol : (atup[j] ? d > opt_tol : d < -opt_tol)) viol.emplace_back(std::fabs(d), static_cast<int32_t>(j));
             }
             for (int64_t i = 0; i < m; ++i) { // non-basic logicals sit at 0: reduced cost -y_i, only '<' rows may move (up)
                 if (vstat[n + i] != 0 || !hlt[i]) continue;
@@ -2332,7 +2334,9 @@ int crossover_band_impl(sx_ctx *ctx, const sx_matrix *A, const double *b, const 
     }
     // ------------------------------------------------------------------ outputs
     std::vector<int8_t> vb(static_cast<size_t>(n)), cb(static_cast<size_t>(m), -1);
-    for (int64_t j = 0; j < n; ++j) vb[j] = vstat[j] == 1 ? 0 : (vstat[j] == 3 ? -3 : (atup[j] ? -2 : -1));
+    // (a non-basic free column sits at no bound: -3, the code it is read with on entry)
+    for (int64_t j = 0; j < n; ++j)
+        vb[j] = vstat[j] == 1 ? 0 : ((vstat[j] == 3 || (std::isinf(hl[j]) && std::isinf(hu[j]))) ? -3 : (atup[j] ? -2 : -1));
     for (int64_t i = 0; i < m; ++i)
         if (vstat[n + i] == 1) cb[i] = 0;
     double obj = 0.0;

@@ -75,6 +75,12 @@ def unpack_price(raw: bytes) -> Tuple[float, int, int]:
     return struct.unpack("<dqq", raw)
 
 
+def resting_bound(l: np.ndarray, u: np.ndarray) -> np.ndarray:
+    """Where a non-basic column rests: at its lower bound, else at its upper bound, else (free) at 0."""
+    l, u = np.asarray(l, dtype=np.float64), np.asarray(u, dtype=np.float64)
+    return np.where(np.isfinite(l), l, np.where(np.isfinite(u), u, 0.0))
+
+
 def reduce_price_records(records: Sequence[Tuple[float, int, int]], offsets: Sequence[int]) -> Tuple[float, int, int]:
     """Global pricing result from per-rank records: smallest reduced cost, ties to the smallest global
     column; ranks without a candidate (argmin < 0: empty block or all NaN) are skipped; counts add."""
@@ -610,7 +616,15 @@ class ShardedLP:
         for the whole LP.  Returns (x over R, y, R, basis over R, status, rounds); ``trace`` collects the columns each
         round added.  Factorisation and tableau are replicated ("replicas only" for those).  ``max_seconds``:
         stop before the next re-solve once ANY rank has spent that long (the flags travel with the record counts, so all
-        ranks leave in the same round): status "TIME_LIMIT", the last vertex returned."""
+        ranks leave in the same round): status "TIME_LIMIT", the last vertex returned.
+
+        Bounds: a column outside R RESTS at x_N = ``resting_bound(l, u)`` -- its lower bound, else its upper bound, else 0
+        (a free column) -- and the restricted LP is solved with the right-hand side b_R = b - A_N x_N: every rank sums its
+        own columns' share, ONE all-reduce of an m-vector before the first round, and the entering columns' share is
+        added back as they enter (they arrive replicated, no further exchange).  The pricing reads the same resting
+        bound (reduced cost < 0 may enter from the lower bound, > 0 from the upper one, either sign for a free column);
+        entering columns are handed over at that bound (-1 / -2), free ones as -3 (superbasic at 0).  The objective of
+        the WHOLE LP is c[R] @ x_R + c_N @ x_N, x_N = resting_bound(l, u) outside R (0 for l = 0)."""
         import time
         import scipy.sparse as sp
         import torch
@@ -645,10 +659,16 @@ class ShardedLP:
         in_R[np.asarray(start_cols, dtype=np.int64)] = True
         R = np.flatnonzero(in_R)
         A_R = fetch(R)
+        # ---- b_R = b - A_N x_N: the own columns outside R at their resting bound, summed over the ranks once
+        rest_all = resting_bound(l_all, u_all)
+        rest_out = np.where(in_R[cs:ce], 0.0, rest_all[cs:ce])
+        share = torch.from_numpy(np.ascontiguousarray(A_loc @ rest_out, dtype=np.float64)).to(dev)
+        self._allreduce(share)
+        b_R = self._b_host - share.cpu().numpy()
         basis, x_R, y, status, rounds = None, None, None, "UNKNOWN", 0
         t_begin = time.perf_counter()
         for rounds in range(1, max_rounds + 1):
-            lp_R = GeneralLP(sp.csr_matrix(A_R), self._b_host, c_all[R], l_all[R], u_all[R], sense)
+            lp_R = GeneralLP(sp.csr_matrix(A_R), b_R, c_all[R], l_all[R], u_all[R], sense)
             # a failure on ONE rank (device memory, a refused basis ...) must not leave the others waiting in the exchange
             # below: it is caught, travels with the record counts, and every rank leaves in this round
             err = None
@@ -664,8 +684,8 @@ class ShardedLP:
             ids_loc, score_loc = np.zeros(0, dtype=np.int64), np.zeros(0)
             if status == "OPTIMAL":
                 x_R, y, basis = np.asarray(out.x, dtype=np.float64), np.asarray(out.y, dtype=np.float64), out.basis
-                # ---- rank-local pricing of the own columns outside R: non-basic at the lower bound (at the upper one when
-                #      there is no lower), reduced cost of the wrong sign = may enter
+                # ---- rank-local pricing of the own columns outside R: non-basic at their resting bound (the lower one, the
+                #      upper one when there is no lower, 0 when there is neither), reduced cost of the wrong sign = may enter
                 rc = np.asarray(o.host(o.dual_slack(self.A_cols, o.vec(y), self.c_loc)), dtype=np.float64)
                 at_up = ~np.isfinite(l_loc) & np.isfinite(u_loc)
                 free = ~np.isfinite(l_loc) & ~np.isfinite(u_loc)
@@ -708,11 +728,12 @@ class ShardedLP:
             vb = np.empty(R_new.size, dtype=np.int64)
             vb[where_old] = basis.vbasis
             up_new = ~np.isfinite(l_all[add]) & np.isfinite(u_all[add])
-            vb[where_add] = np.where(up_new, -2, -1)
+            free_new = ~np.isfinite(l_all[add]) & ~np.isfinite(u_all[add])
+            vb[where_add] = np.where(free_new, -3, np.where(up_new, -2, -1))
             x_new = np.empty(R_new.size)
             x_new[where_old] = x_R
-            bound = np.where(up_new, u_all[add], l_all[add])
-            x_new[where_add] = np.where(np.isfinite(bound), bound, 0.0)
+            x_new[where_add] = rest_all[add]
+            b_R = b_R + A_add @ rest_all[add]            # they leave N: their share of A_N x_N goes back
             basis, x_R, R = Basis(vb, basis.cbasis), x_new, R_new
         return x_R, y, R, basis, status, rounds
 

@@ -2,6 +2,7 @@
 `world` ranks -- restricted LP replicated (solved by HiGHS here, by the device solvers on the GPU), pricing of the other
 columns rank-local (played by the CPU oracle), one all-gather of the pricing records and one of the entering columns per
 round; rank 0 writes the rounds' columns and the optimum."""
+import dataclasses
 import json
 import os
 import sys
@@ -26,8 +27,29 @@ def problem(m=600, n=6000, seed=17):
     rng = np.random.default_rng(seed + 1)
     c = inst.c + 0.3 * rng.standard_normal(n)
     u = np.where(np.isinf(inst.u), 30.0, inst.u)
-    lp = GeneralLP(inst.A, inst.b, c, inst.l, u, inst.sense)
     start = np.flatnonzero(inst.x > 1e-6)          # the interior columns of the point: a feasible restricted LP
+    mode = os.environ.get("SX_TEST_BOUNDS")
+    if mode in ("image", "image-open"):
+        # the same LP under x = d * x' + t (tests/_general_bounds.py): non-zero resting bounds, boxes that straddle 0.
+        # The start is chosen by the same rule: the columns the point does not leave at the bound they would rest at
+        # outside the restricted LP (above, with l = 0: x > 1e-6) -- a mirrored column at its upper bound is among them
+        from _general_bounds import affine_image, free_some, highs
+        inst, _, _, _ = affine_image(dataclasses.replace(inst, c=c, u=u, x=np.clip(inst.x, inst.l, u)), 5)
+        if mode == "image-open":
+            # bounds that are not active at the optimum taken away (the optimum stays where it is): the columns at their
+            # upper bound both at the point and at the optimum lose their lower bound -- UPPER-ONLY columns that rest at u
+            # outside the restricted LP --, the columns at l = 0 at the point that the optimum holds strictly inside their
+            # box lose both -- FREE columns that rest at 0 outside it and have to enter
+            ref = highs(inst)
+            assert ref.status == 0
+            at_up = (np.abs(inst.u - inst.x) <= 1e-6) & (np.abs(inst.u - ref.x) <= 1e-9)
+            inside = (inst.l == 0.0) & (np.abs(inst.x) <= 1e-6) & (ref.x > inst.l + 1e-3) & (ref.x < inst.u - 1e-3)
+            l = inst.l.copy()
+            l[at_up] = -np.inf
+            inst = free_some(dataclasses.replace(inst, l=l), np.flatnonzero(inside))
+        c, u = inst.c, inst.u
+        start = np.flatnonzero(np.abs(inst.x - D.resting_bound(inst.l, inst.u)) > 1e-6)
+    lp = GeneralLP(inst.A, inst.b, c, inst.l, u, inst.sense)
     problem.point = (inst.x, inst.y)
     return lp, start
 
@@ -83,8 +105,10 @@ def main():
             dist.destroy_process_group()
         return
     x_R, y, R, basis, status, rounds = sh.restricted_resolve(start, solver=solver, batch=batch, opt_tol=1e-7, trace=trace, **kw)
+    x_all = D.resting_bound(lp.l, lp.u)            # the columns outside R rest at a bound: c_N @ x_N is part of the objective
+    x_all[R] = x_R
     res = {"world": 1 if single else dist.get_world_size(), "status": status, "rounds": rounds, "trace": trace,
-           "obj": float(lp.c[R] @ x_R), "R": [int(j) for j in R], "basic": [int(j) for j in R[basis.vbasis == 0]]}
+           "obj": float(lp.c @ x_all), "R": [int(j) for j in R], "basic": [int(j) for j in R[basis.vbasis == 0]]}
     if single or dist.get_rank() == 0:
         with open(out_path, "w") as f:
             json.dump(res, f)

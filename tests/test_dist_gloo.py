@@ -147,6 +147,77 @@ def test_column_sharded_re_solve_adds_the_single_process_columns(tmp_path):
         assert res["obj"] == pytest.approx(single["obj"], rel=1e-12)
 
 
+def test_column_sharded_re_solve_with_columns_resting_at_non_zero_bounds(tmp_path, monkeypatch):
+    """The same LP under x = d * x' + t (tests/_general_bounds.py, pinned by tests/test_general_bounds_cpu.py): the columns
+    outside the restricted LP rest at non-zero lower bounds, or at their upper bound where there is no lower one, so its
+    right-hand side is b - A_N x_N and the objective of the whole LP c[R] @ x_R + c_N @ x_N.  (With b unchanged the loop
+    ends "OPTIMAL" on a vertex of another LP: -5728.25 with rows violated by 24.3, HiGHS' optimum is -5934.80; started
+    from the strictly interior columns alone it is INFEASIBLE in round 1.)  One process: OPTIMAL in >= 3 rounds at
+    HiGHS' optimum of the image; two and three gloo ranks add the same columns in the same rounds and end on the same
+    basis."""
+    import importlib.util
+    import numpy as np
+    from scipy.optimize import linprog
+    env = {"SX_TEST_BATCH": "64", "SX_TEST_BOUNDS": "image"}
+    single = run_workers("_dist_worker4.py", tmp_path / "w1.json", 1, env)
+    assert single["status"] == "OPTIMAL" and single["rounds"] >= 3 and all(0 < len(t) <= 64 for t in single["trace"])
+    spec = importlib.util.spec_from_file_location("w4", os.path.join(HERE, "_dist_worker4.py"))
+    w4 = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(w4)
+    with monkeypatch.context() as mp:
+        mp.setenv("SX_TEST_BOUNDS", "image")
+        lp, start = w4.problem()
+    # what the image is for: non-zero resting bounds OUTSIDE the start set, of both signs
+    out = np.ones(lp.c.size, dtype=bool)
+    out[start] = False
+    assert np.count_nonzero(out & (lp.l < -1e-3)) > 100 and np.count_nonzero(out & (lp.l > 1e-3)) > 100
+    lt = np.asarray(lp.sense) == "<"
+    fin = lambda v: [None if np.isinf(s) else float(s) for s in v]   # noqa: E731
+    ref = linprog(lp.c, A_ub=lp.A[lt], b_ub=lp.b[lt], A_eq=lp.A[~lt], b_eq=lp.b[~lt], bounds=list(zip(fin(lp.l), fin(lp.u))), method="highs")
+    assert ref.status == 0 and single["obj"] == pytest.approx(ref.fun, rel=1e-8)
+    for world in (2, 3):
+        res = run_workers("_dist_worker4.py", tmp_path / f"w{world}.json", world, env)
+        assert res["world"] == world and res["status"] == "OPTIMAL"
+        assert res["trace"] == single["trace"] and res["R"] == single["R"]
+        assert res["basic"] == single["basic"]
+        assert res["obj"] == pytest.approx(single["obj"], rel=1e-12)
+
+
+def test_column_sharded_re_solve_with_upper_only_and_free_columns_outside(tmp_path, monkeypatch):
+    """The image with the bounds that are not active at its optimum taken away (`SX_TEST_BOUNDS=image-open`): upper-only
+    columns rest at u outside the restricted LP, free ones at 0 and enter whatever the sign of their reduced cost, handed
+    over as -3.  Same optimum as HiGHS on the whole LP; two gloo ranks do what one process does."""
+    import importlib.util
+    import numpy as np
+    from scipy.optimize import linprog
+    env = {"SX_TEST_BATCH": "64", "SX_TEST_BOUNDS": "image-open"}
+    single = run_workers("_dist_worker4.py", tmp_path / "w1.json", 1, env)
+    assert single["status"] == "OPTIMAL" and single["rounds"] >= 3
+    spec = importlib.util.spec_from_file_location("w4", os.path.join(HERE, "_dist_worker4.py"))
+    w4 = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(w4)
+    with monkeypatch.context() as mp:
+        mp.setenv("SX_TEST_BOUNDS", "image-open")
+        lp, start = w4.problem()
+    n = lp.c.size
+    at_start, at_end = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+    at_start[start], at_end[single["R"]] = True, True
+    upper_only, free = np.isinf(lp.l) & np.isfinite(lp.u), np.isinf(lp.l) & np.isinf(lp.u)
+    assert np.count_nonzero(upper_only & ~at_end & (lp.u != 0)) > 100         # rested at a non-zero u to the end
+    assert np.count_nonzero(free & ~at_start) > 20 and np.all(at_end[free])   # every free column had to enter ...
+    basic = np.zeros(n, dtype=bool)
+    basic[single["basic"]] = True
+    assert np.all(basic[free])                                                # ... and is basic at the optimum
+    lt = np.asarray(lp.sense) == "<"
+    fin = lambda v: [None if np.isinf(s) else float(s) for s in v]   # noqa: E731
+    ref = linprog(lp.c, A_ub=lp.A[lt], b_ub=lp.b[lt], A_eq=lp.A[~lt], b_eq=lp.b[~lt], bounds=list(zip(fin(lp.l), fin(lp.u))), method="highs")
+    assert ref.status == 0 and single["obj"] == pytest.approx(ref.fun, rel=1e-8)
+    res = run_workers("_dist_worker4.py", tmp_path / "w2.json", 2, env)
+    assert res["world"] == 2 and res["status"] == "OPTIMAL"
+    assert res["trace"] == single["trace"] and res["R"] == single["R"] and res["basic"] == single["basic"]
+    assert res["obj"] == pytest.approx(single["obj"], rel=1e-12)
+
+
 def test_a_failing_rank_takes_every_rank_out_of_the_sharded_resolve(tmp_path):
     """One rank's replicated solve raises in the second round: the failure travels with the record counts, the failing rank
     re-raises its own exception, the others a RuntimeError naming it -- and nobody waits in an all-gather (the bench's

@@ -124,3 +124,32 @@ def test_column_sharded_re_solve_on_the_device(tmp_path):
     lt = np.asarray(lp.sense) == "<"
     ref = linprog(lp.c, A_ub=lp.A[lt], b_ub=lp.b[lt], A_eq=lp.A[~lt], b_eq=lp.b[~lt], bounds=np.c_[lp.l, lp.u], method="highs")
     assert ref.status == 0 and res["obj"] == pytest.approx(ref.fun, rel=1e-7, abs=1e-7)
+
+
+def test_column_sharded_re_solve_on_the_device_with_columns_resting_at_non_zero_bounds(tmp_path, monkeypatch):
+    """The same leg on the image of that LP under x = d * x' + t (tests/_general_bounds.py): the columns outside the restricted
+    LP rest at non-zero bounds, its right-hand side is b - A_N x_N (one all-reduce), the entering columns are handed to
+    sx_crossover_band_basis_dev at shifted and mirrored bounds.  Two ranks as one process; HiGHS' optimum of the whole
+    image, c_N @ x_N included."""
+    import importlib.util
+    import numpy as np
+    from scipy.optimize import linprog
+    sys.path.insert(0, HERE)
+    from test_dist_gloo import run_workers
+    env = {"SX_DIST_OPS": "hip", "SX_TEST_SOLVER": "HIP", "SX_TEST_SIZE": "2400,24000", "SX_TEST_BATCH": "128",
+           "HSA_ENABLE_IPC_MODE_LEGACY": "0", "LOCAL_RANK": "0", "SX_TEST_BOUNDS": "image"}
+    single = run_workers("_dist_worker4.py", tmp_path / "w1.json", 1, env)
+    assert single["status"] == "OPTIMAL" and single["rounds"] >= 2
+    res = run_workers("_dist_worker4.py", tmp_path / "w2.json", 2, env)
+    assert res["world"] == 2 and res["status"] == "OPTIMAL"
+    assert res["trace"] == single["trace"] and res["R"] == single["R"] and res["basic"] == single["basic"]
+    spec = importlib.util.spec_from_file_location("w4", os.path.join(HERE, "_dist_worker4.py"))
+    w4 = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(w4)
+    with monkeypatch.context() as mp:
+        mp.setenv("SX_TEST_BOUNDS", "image")
+        lp, start = w4.problem(2400, 24000)
+    assert np.count_nonzero(lp.l != 0) > 10000
+    lt = np.asarray(lp.sense) == "<"
+    ref = linprog(lp.c, A_ub=lp.A[lt], b_ub=lp.b[lt], A_eq=lp.A[~lt], b_eq=lp.b[~lt], bounds=np.c_[lp.l, lp.u], method="highs")
+    assert ref.status == 0 and res["obj"] == pytest.approx(ref.fun, rel=1e-7, abs=1e-7)
