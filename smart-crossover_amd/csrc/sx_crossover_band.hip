@@ -3,8 +3,7 @@
 // their crossover behind the barrier (lp_methods/algorithms.py:50-54 -> solver_caller/gurobi.py:111-115) and their
 // warm-started simplex (lp_methods/algorithms.py:69-74), all inside Gurobi.
 //
-// Rounds 1-2 kept B^-1 explicitly (8 m^2 bytes); round 3 factored a band basis once, covered the dense (linking) rows by
-// their logicals and paid for it with one pivot per linking row on a 66-99 GB tableau.  Now:
+// The design:
 //   * the basis is factored in BORDERED form (sx_border.h): rows in their natural (or Cuthill-McKee) order, dense rows set
 //     aside; every basic variable is matched to a band row by entry size -> B11, a band matrix (K16f); what finds no band
 //     row -- the linking activities, logicals of dense rows -- forms the border together with the dense rows, and the
@@ -23,8 +22,15 @@
 //     checked against A itself; beyond the tolerances the basis is factored afresh and the run goes on.
 // Memory O(nnz + m (kl + ku) + nb^2 + m |J|).  Everything that decides a pivot runs on the device; the host replays
 // batches of pivots and reads one status word per batch.
+//
+// The file: kernels first; then the state of a call (HostLp, BandCall), of the basis (sx_plan::BasisState) and of one epoch
+// (Epoch: device arrays, factors, border operators, tableau -- owned in one place); then one function per stage, and
+// crossover_band_impl, which is the list of the stages and the three ways an epoch goes round again.  The host set-up
+// between the device stages -- row order, matching, block geometry, triplets, the bookkeeping after the two LUs -- is
+// sx_band_plan.h: plain C++ over vectors, tested on the CPU, and the seam a device-side set-up would replace.
 #include "sx_internal.h"
 #include "sx_border.h"
+#include "sx_band_plan.h"
 
 #include <algorithm>
 #include <cstring>
@@ -993,26 +999,31 @@ struct BigArena {
 };
 
 // per-slot arrays of the tableau (one slot per tracked column) and the tableau itself; grown when pricing brings in more
-// columns than there is room for (the explicit tableau of round 3 was sized once, at 90 % of the free memory)
-struct TbSlots {
+// columns than there is room for.  THE list of the per-slot arrays -- (type, name, entries per slot) -- in the order they
+// are allocated and freed; T, the tableau, comes before them
+#define TB_SLOT_ARRAYS(X)                                                                                                          \
+    X(double, xJ, 1) X(double, lJ, 1) X(double, uJ, 1) X(double, cJ, 1) X(double, dJ, 1) X(double, d1, 1) X(double, rowbuf, 1)     \
+    X(double, vbuf, TB_K) X(double, ebG, TB_EB) X(double, ebS, TB_EB)                                                             \
+    X(int32_t, varJ, 1) X(int32_t, statJ, 1) X(int32_t, s0, 1) X(int32_t, sbase, 1) X(int32_t, elist, 1)
+struct TbSlotArrays {
     int64_t mp = 0, cap = 0;
     bool T_own = true; // false: T is a piece of the call's arena
-    double *T = nullptr, *xJ = nullptr, *lJ = nullptr, *uJ = nullptr, *cJ = nullptr, *dJ = nullptr, *d1 = nullptr, *rowbuf = nullptr,
-           *vbuf = nullptr, *ebG = nullptr, *ebS = nullptr;
-    int32_t *varJ = nullptr, *statJ = nullptr, *s0 = nullptr, *sbase = nullptr, *elist = nullptr;
+    double *T = nullptr;
+#define TB_DECLARE(type, name, per) type *name = nullptr;
+    TB_SLOT_ARRAYS(TB_DECLARE)
+#undef TB_DECLARE
+};
+struct TbSlots : TbSlotArrays {
     TbSlots() = default;
     TbSlots(const TbSlots &) = delete;
     TbSlots &operator=(const TbSlots &) = delete;
     ~TbSlots() {
-        for (void *q : {(void *)(T_own ? T : nullptr), (void *)xJ, (void *)lJ, (void *)uJ, (void *)cJ, (void *)dJ, (void *)d1, (void *)rowbuf, (void *)vbuf, (void *)ebG,
-                        (void *)ebS, (void *)varJ, (void *)statJ, (void *)s0, (void *)sbase, (void *)elist})
-            (void)sx_dfree(q);
+        if (T_own) (void)sx_dfree(T);
+#define TB_FREE(type, name, per) (void)sx_dfree(name);
+        TB_SLOT_ARRAYS(TB_FREE)
+#undef TB_FREE
     }
-    void swap_with(TbSlots &o) {
-        std::swap(mp, o.mp); std::swap(cap, o.cap); std::swap(T_own, o.T_own); std::swap(T, o.T); std::swap(xJ, o.xJ); std::swap(lJ, o.lJ); std::swap(uJ, o.uJ);
-        std::swap(cJ, o.cJ); std::swap(dJ, o.dJ); std::swap(d1, o.d1); std::swap(rowbuf, o.rowbuf); std::swap(vbuf, o.vbuf); std::swap(ebG, o.ebG);
-        std::swap(ebS, o.ebS); std::swap(varJ, o.varJ); std::swap(statJ, o.statJ); std::swap(s0, o.s0); std::swap(sbase, o.sbase); std::swap(elist, o.elist);
-    }
+    void swap_with(TbSlots &o) { std::swap(static_cast<TbSlotArrays &>(*this), static_cast<TbSlotArrays &>(o)); }
     static size_t bytes_for(int64_t mp_, int64_t cap_) {
         return sizeof(double) * (static_cast<size_t>(mp_) * cap_ + static_cast<size_t>(7 + TB_K + 2 * TB_EB) * cap_) + sizeof(int32_t) * 5 * static_cast<size_t>(cap_);
     }
@@ -1027,18 +1038,16 @@ struct TbSlots {
             nw.T = static_cast<double *>(arena->take(sizeof(double) * static_cast<size_t>(mp_) * c));
             nw.T_own = nw.T == nullptr;
         }
-#define TB_GET(field, count)                                                                                                       \
-    if (sx_dmalloc(reinterpret_cast<void **>(&nw.field), sizeof(*nw.field) * (count)) != hipSuccess) {                               \
+#define TB_GET(type, field, per)                                                                                                   \
+    if (sx_dmalloc(reinterpret_cast<void **>(&nw.field), sizeof(type) * (static_cast<size_t>(per) * c)) != hipSuccess) {           \
         sx_set_error("hipMalloc of %zu bytes failed in the sparse crossover (tableau of %lld columns over %lld positions)",        \
-                     sizeof(*nw.field) * (count), (long long)newcap, (long long)mp_);                                              \
+                     sizeof(type) * (static_cast<size_t>(per) * c), (long long)newcap, (long long)mp_);                            \
         return SX_ERR_NOMEM;                                                                                                       \
     }
-        if (!nw.T) TB_GET(T, static_cast<size_t>(mp_) * c)
-        TB_GET(xJ, c) TB_GET(lJ, c) TB_GET(uJ, c) TB_GET(cJ, c) TB_GET(dJ, c) TB_GET(d1, c) TB_GET(rowbuf, c)
-        TB_GET(vbuf, static_cast<size_t>(TB_K) * c) TB_GET(ebG, static_cast<size_t>(TB_EB) * c) TB_GET(ebS, static_cast<size_t>(TB_EB) * c)
-        TB_GET(varJ, c) TB_GET(statJ, c) TB_GET(s0, c) TB_GET(sbase, c) TB_GET(elist, c)
+        if (!nw.T) TB_GET(double, T, mp_)
+        TB_SLOT_ARRAYS(TB_GET)
 #undef TB_GET
-        if (keep > 0) {
+        if (keep > 0) { // (what a slot carries from round to round; the other arrays are scratch)
             SX_REQUIRE(mp_ == mp && keep <= cap, "internal: tableau columns cannot be carried over");
             const size_t k = static_cast<size_t>(keep);
             SX_HIP(hipMemcpyAsync(nw.T, T, sizeof(double) * static_cast<size_t>(mp_) * k, hipMemcpyDeviceToDevice, s));
@@ -1058,46 +1067,977 @@ struct TbSlots {
     }
 };
 
-// rows of a sparse matrix from (row, index, value) triplets (counting sort, stable); `list` != nullptr: only the rows
-// that hold an entry, listed in ascending order
-struct HostRows {
-    std::vector<int64_t> ptr;
-    std::vector<int32_t> idx, list;
-    std::vector<double> val;
+namespace pl = sx_plan;
+
+// ---------------------------------------------------------------------------------------------- state of a call
+// host copies of the LP (once per call).  Variables: [0, n) columns of A, n + i the logical of row i ('<' rows: >= 0, others 0)
+struct HostLp {
+    int64_t m = 0, n = 0, nnz = 0;
+    std::vector<int64_t> cptr, rptr;
+    std::vector<int32_t> cidx;
+    std::vector<double> cval, b, c, l, u;
+    std::vector<uint8_t> lt;
+    std::vector<int8_t> vb_in, cb_in;
+    double lo(int64_t v) const { return v < n ? l[v] : 0.0; }
+    double up(int64_t v) const { return v < n ? u[v] : (lt[v - n] ? INFINITY : 0.0); }
+    double cost(int64_t v) const { return v < n ? c[v] : 0.0; }
+    pl::Csc csc() const { return pl::Csc{m, n, cptr.data(), cidx.data(), cval.data()}; }
 };
-void rows_from_triplets(int64_t nrows, const std::vector<int32_t> &row, const std::vector<int32_t> &idx, const std::vector<double> &val, bool compact,
-                        HostRows &out) {
-    std::vector<int64_t> cnt(static_cast<size_t>(nrows) + 1, 0);
-    for (int32_t r : row) ++cnt[static_cast<size_t>(r) + 1];
-    for (int64_t r = 0; r < nrows; ++r) cnt[r + 1] += cnt[r];
-    out.idx.assign(row.size(), 0);
-    out.val.assign(row.size(), 0.0);
-    std::vector<int64_t> at(cnt.begin(), cnt.end() - 1);
-    for (size_t e = 0; e < row.size(); ++e) {
-        const int64_t o = at[row[e]]++;
-        out.idx[o] = idx[e];
-        out.val[o] = val[e];
+
+// what lives as long as the call: arguments, device blocks, counters, the verdict so far
+struct BandCall {
+    sx_ctx *ctx = nullptr;
+    const sx_matrix *A = nullptr;
+    const double *b = nullptr, *c = nullptr; // (device)
+    hipStream_t s = nullptr;
+    bool trace = false, given = false;
+    double t_begin = 0.0;
+    int64_t m = 0, n = 0, max_iter = 0;
+    double feas_tol = 0.0, opt_tol = 0.0;
+    // smallest pivot the two LUs accept.  A GUESSED basis (the m largest margins of a first-order point) may hold columns
+    // that are all but dependent -- its basic solution then lies far from the point and phase 1 pays for it pivot by pivot
+    // -- so its LUs set such columns aside (they stay superbasic, a logical takes their place); a basis the simplex has
+    // reached, or one that was given, is kept unless it is singular to working accuracy
+    double tol_band_guess = 1e-3, tol_schur_guess = 1e-1;
+    static constexpr double tol_band_keep = 1e-7, tol_schur_keep = 1e-9;
+    DevBufs dev; // lives as long as the call
+    BigArena arena;
+    double *d_tmpm = nullptr, *d_tmpn = nullptr, *d_rc = nullptr, *d_gu = nullptr, *d_ebM = nullptr;
+    TbState *d_st = nullptr;
+    int32_t *d_pr = nullptr;
+    long long tot_iters = 0, tot_pivots = 0, tot_flips = 0, tot_degen = 0;
+    int64_t added_total = 0;
+    int epochs = 0, final_status = 4, bad_epochs = 0, check_epochs = 0;
+    std::vector<double> hy, hslack;
+    double viol_max = 0.0, resid_max = 0.0;
+    size_t peak_bytes = 0;
+    bool strict_next = false, strict_tried = false;
+    static double now() {
+        timespec ts;
+        clock_gettime(CLOCK_MONOTONIC, &ts);
+        return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
     }
-    out.ptr.clear();
-    out.list.clear();
-    if (!compact) {
-        out.ptr = cnt;
-        return;
-    }
-    out.ptr.push_back(0);
-    for (int64_t r = 0; r < nrows; ++r)
-        if (cnt[r + 1] > cnt[r]) {
-            out.list.push_back(static_cast<int32_t>(r));
-            out.ptr.push_back(cnt[r + 1]);
+    double ms() const { return now() - t_begin; }
+};
+
+// One epoch: a factorisation of the current basic set and the simplex rounds on it.  The device side is released in the
+// reverse order of the members: tableau, border operators, the two LUs, then the epoch's arrays.
+struct Epoch {
+    DevBufs dev;
+    struct Factors {
+        sx_bandlu *lu = nullptr;
+        sx_denselu *dl = nullptr;
+        ~Factors() {
+            if (lu) sx_bandlu_destroy(lu);
+            if (dl) sx_denselu_destroy(dl);
         }
+    } fac;
+    SxBorderOps ops;
+    TbSlots sl;
+    // the plan (sx_band_plan.h)
+    pl::Matching mt;
+    pl::EpochGeometry g;
+    pl::BandTriplets tri;
+    std::vector<int32_t> ph_row; // the row whose unit vector a placeholder is
+    pl::Border bd;
+    std::vector<int64_t> head;
+    std::vector<int32_t> varJ;
+    int64_t nrep = 0, nb = 0, mp = 0, nJ = 0, n_dummy = 0, EPOCH = 0;
+    // device arrays over the positions
+    int nblk = 0;
+    int32_t *d_eqidx = nullptr, *d_eta_r = nullptr, *d_head = nullptr, *d_blist = nullptr, *d_infoff = nullptr, *d_inflist = nullptr;
+    double *d_eta = nullptr, *d_xB = nullptr, *d_lB = nullptr, *d_uB = nullptr, *d_cB = nullptr, *d_g = nullptr, *d_vec = nullptr, *d_part = nullptr,
+           *d_infpart = nullptr, *d_etp = nullptr;
+    TbPart *d_rpart = nullptr;
+    // the simplex rounds and what they leave
+    TbState hst{};
+    bool restart = false;
+    std::vector<double> hrc; // reduced costs of the structural columns under the last duals
+    std::vector<int32_t> hh, hvarJ, hstatJ;
+    std::vector<double> hxb, hxJ;
+};
+
+// ---------------------------------------------------------------------------------------------- helpers
+// b - A x to the host (one K2 walk), synchronised.  x on the device ...
+int slack_to_host(BandCall &C, const double *d_x, std::vector<double> &out) {
+    SX_TRY(sx_score_rows_dev(C.ctx, C.A, d_x, C.b, nullptr, 0.0, C.d_tmpm, nullptr));
+    SX_TRY(down(C.s, out, C.d_tmpm, static_cast<size_t>(C.m)));
+    SX_HIP(hipStreamSynchronize(C.s));
+    return SX_OK;
+}
+// ... or on the host
+int slack_to_host(BandCall &C, const std::vector<double> &x, std::vector<double> &out) {
+    SX_TRY(up(C.s, C.d_tmpn, x));
+    return slack_to_host(C, C.d_tmpn, out);
+}
+// vstat from the device's head / varJ: 1 basic, 2 tracked (3: tracked and superbasic, when the slots' status is given)
+void vstat_from_device(const std::vector<int32_t> &hh, const std::vector<int32_t> &hvarJ, const std::vector<int32_t> *hstatJ, std::vector<int8_t> &vstat) {
+    std::fill(vstat.begin(), vstat.end(), 0);
+    for (int32_t v : hh)
+        if (v >= 0) vstat[v] = 1;
+    for (size_t t = 0; t < hvarJ.size(); ++t) vstat[hvarJ[t]] = (hstatJ && (*hstatJ)[t] == TB_SUP) ? 3 : 2;
+}
+// the basic variables' values -> the point; returns the largest bound violation among them
+double basic_values_to_point(const HostLp &lp, const std::vector<int32_t> &hh, const std::vector<double> &hxb, std::vector<double> &hx) {
+    double viol = 0.0;
+    for (size_t p = 0; p < hh.size(); ++p) {
+        const int64_t v = hh[p];
+        if (v < 0) continue;
+        viol = std::max(viol, std::max(lp.lo(v) - hxb[p], hxb[p] - lp.up(v)));
+        if (v < lp.n) hx[v] = hxb[p];
+    }
+    return viol;
+}
+// largest row residual of the point whose slacks are hslack, relative to 1 + |b_i|
+double row_residual(const HostLp &lp, const std::vector<double> &hslack) {
+    double worst = 0.0;
+    for (int64_t i = 0; i < lp.m; ++i) {
+        const double sc = 1.0 + std::fabs(lp.b[i]);
+        const double r = lp.lt[i] ? std::max(-hslack[i], 0.0) : std::fabs(hslack[i]);
+        worst = std::max(worst, r / sc);
+    }
+    return worst;
+}
+// columns of the eta file that 16 GB, or 0.4 of the free memory, hold over mp positions (the arena's estimate and the
+// epoch's real length both start from this)
+double eta_columns_by_memory(size_t free_b, double mp) { return std::min(16.0e9, 0.4 * static_cast<double>(free_b)) / (8.0 * mp); }
+
+int rows_to_dev(BandCall &C, Epoch &E, const pl::HostRows &R, int64_t nrows, bool with_list, SxRowsDev &out) {
+    int64_t *dp = nullptr;
+    int32_t *di = nullptr, *dlist = nullptr;
+    double *dv = nullptr;
+    SX_TRY(E.dev.get(R.ptr.size(), &dp));
+    SX_TRY(E.dev.get(R.idx.size(), &di));
+    SX_TRY(E.dev.get(R.val.size(), &dv));
+    SX_TRY(up(C.s, dp, R.ptr));
+    SX_TRY(up(C.s, di, R.idx));
+    SX_TRY(up(C.s, dv, R.val));
+    if (with_list) {
+        SX_TRY(E.dev.get(R.list.size(), &dlist));
+        SX_TRY(up(C.s, dlist, R.list));
+    }
+    out.nrows = nrows;
+    out.ptr = dp;
+    out.idx = di;
+    out.val = dv;
+    out.list = dlist;
+    return SX_OK;
 }
 
-} // namespace
+// solve helper: row-space columns through the bordered factors, then the eta file
+int ftran_cols(BandCall &C, Epoch &E, double *W, int64_t ncols, int64_t n_eta_now, bool lp_columns) {
+    if (ncols == 0) return SX_OK;
+    hipStream_t s = C.s;
+    const int64_t mp = E.mp;
+    SX_TRY(E.ops.ftran(W, ncols, lp_columns));
+    if (n_eta_now > 0) { // (what the tableau would drop anyway goes first: the list of an eta holds real entries only)
+        hipLaunchKernelGGL(k_tb_drop, dim3(gridcap(mp * ncols)), dim3(TB_WG), 0, s, mp * ncols, W, TB_DROP);
+    }
+    for (int64_t k0 = 0; k0 < n_eta_now; k0 += TB_EB) {
+        const int K = static_cast<int>(std::min<int64_t>(TB_EB, n_eta_now - k0));
+        hipLaunchKernelGGL(k_tb_etab_gather, dim3(gridof(std::max<int64_t>(TB_EB * ncols, TB_EB * TB_EB))), dim3(TB_WG), 0, s, mp, ncols, W, E.d_eta,
+                           E.d_eta_r, k0, K, E.sl.ebG, C.d_ebM);
+        hipLaunchKernelGGL(k_tb_etab_solve, dim3(static_cast<unsigned>((ncols + 63) / 64)), dim3(64), 0, s, ncols, E.sl.ebG, C.d_ebM, E.sl.ebS, E.sl.elist);
+        hipLaunchKernelGGL(k_tb_etab_apply, dim3(static_cast<unsigned>(std::min(E.nblk, 1024)), static_cast<unsigned>((ncols + TB_EC - 1) / TB_EC)),
+                           dim3(TB_WG), 0, s, mp, ncols, W, E.d_eta, E.d_eta_r, k0, K, E.sl.ebS, E.sl.elist);
+    }
+    SX_HIP(hipGetLastError());
+    return SX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- stages before the epochs
+// The question "would the band LU take the matched basis?" has a sufficient answer in the matrix alone: no column of
+// A is taller (over the rows that are not dense) than a band the LU takes, so no basis is.  One kernel instead of the
+// host copies, the row order and the matching (18 ms at 1e5 rows); a matrix that fails it gets the full answer
+int probe_shortcut(BandCall &C, bool &taken) {
+    const sx_matrix *A = C.A;
+    const int64_t dense_thr = pl::dense_threshold(A->nnz, C.m);
+    int *d_q = nullptr;
+    SX_TRY(C.dev.get(2, &d_q));
+    SX_HIP(hipMemsetAsync(d_q, 0, 2 * sizeof(int), C.s));
+    hipLaunchKernelGGL(k_tb_colspan, dim3(gridof(std::max(C.m, C.n))), dim3(TB_WG), 0, C.s, C.m, C.n, A->csc_ptr, A->csc_idx, A->csr_ptr, dense_thr, d_q);
+    int hq[2] = {0, 0};
+    SX_HIP(hipMemcpyAsync(hq, d_q, sizeof(hq), hipMemcpyDeviceToHost, C.s));
+    SX_HIP(hipStreamSynchronize(C.s));
+    if (C.trace) fprintf(stderr, "[sx_crossover_band] probe: tallest column %d rows outside the %d dense rows\n", hq[0], hq[1]);
+    taken = hq[1] <= pl::MAX_NB / 2 && sx_bandlu_supports(hq[0], hq[0]);
+    return SX_OK;
+}
+
+int host_copies(BandCall &C, const double *l, const double *u, const uint8_t *row_is_lt, const double *x_start, const int8_t *vbasis_in,
+                const int8_t *cbasis_in, HostLp &lp, pl::BasisState &bs) {
+    const sx_matrix *A = C.A;
+    hipStream_t s = C.s;
+    const int64_t m = C.m, n = C.n;
+    lp.m = m;
+    lp.n = n;
+    lp.nnz = A->nnz;
+    lp.lt.assign(static_cast<size_t>(m), 0);
+    SX_TRY(down(s, lp.cptr, A->csc_ptr, static_cast<size_t>(n) + 1));
+    SX_TRY(down(s, lp.rptr, A->csr_ptr, static_cast<size_t>(m) + 1));
+    SX_TRY(down(s, lp.cidx, A->csc_idx, static_cast<size_t>(A->nnz)));
+    SX_TRY(down(s, lp.cval, A->csc_val, static_cast<size_t>(A->nnz)));
+    SX_TRY(down(s, lp.b, C.b, static_cast<size_t>(m)));
+    SX_TRY(down(s, lp.c, C.c, static_cast<size_t>(n)));
+    SX_TRY(down(s, lp.l, l, static_cast<size_t>(n)));
+    SX_TRY(down(s, lp.u, u, static_cast<size_t>(n)));
+    SX_TRY(down(s, bs.hx, x_start, static_cast<size_t>(n)));
+    if (row_is_lt) SX_HIP(hipMemcpyAsync(lp.lt.data(), row_is_lt, static_cast<size_t>(m), hipMemcpyDeviceToHost, s));
+    if (vbasis_in) {
+        SX_TRY(down(s, lp.vb_in, vbasis_in, static_cast<size_t>(n)));
+        SX_TRY(down(s, lp.cb_in, cbasis_in, static_cast<size_t>(m)));
+    }
+    SX_TRY(C.dev.get(static_cast<size_t>(m), &C.d_tmpm));
+    SX_TRY(C.dev.get(static_cast<size_t>(n), &C.d_tmpn));
+    SX_TRY(C.dev.get(static_cast<size_t>(n), &C.d_rc));
+    SX_HIP(hipStreamSynchronize(s));
+    for (int64_t j = 0; j < n; ++j) bs.hx[j] = std::min(std::max(bs.hx[j], lp.l[j]), lp.u[j]);
+    return SX_OK;
+}
+
+// dense rows, band rows and the order of the band rows (once per call)
+int plan_rows(BandCall &C, const HostLp &lp, pl::RowPlan &rp) {
+    const sx_matrix *A = C.A;
+    const int64_t dense_thr = pl::dense_threshold(A->nnz, C.m);
+    pl::classify_rows(C.m, lp.rptr.data(), dense_thr, rp);
+    const int64_t m1 = static_cast<int64_t>(rp.rows_band.size()), ndr = static_cast<int64_t>(rp.rows_dense.size());
+    if (ndr > pl::MAX_NB) {
+        sx_set_error("%lld rows with more than %lld entries: the border of the basis would pass the dense LU's %lld rows", (long long)ndr,
+                     (long long)dense_thr, (long long)pl::MAX_NB);
+        return SX_ERR_UNSUPPORTED;
+    }
+    const int32_t tall_nat = pl::tallest(lp.csc(), rp.rows_band);
+    if (tall_nat > pl::CM_TRIGGER && m1 > 1) { // (the rows of A by row come to the host only when they are needed)
+        std::vector<int32_t> ridx, cm;
+        SX_TRY(down(C.s, ridx, A->csr_idx, static_cast<size_t>(A->nnz)));
+        SX_HIP(hipStreamSynchronize(C.s));
+        if (pl::cuthill_mckee_order(lp.csc(), lp.rptr.data(), ridx.data(), A->nnz, rp.rows_band, cm)) {
+            const int32_t tall_cm = pl::tallest(lp.csc(), cm);
+            if (C.trace) fprintf(stderr, "[sx_crossover_band] tallest column: %d rows in natural order, %d in Cuthill-McKee order\n", tall_nat, tall_cm);
+            if (tall_cm < tall_nat) rp.rows_band = cm;
+        }
+    }
+    pl::finish_row_plan(C.m, rp);
+    int32_t *d_eqidx = nullptr;
+    SX_TRY(C.dev.get(rp.eqidx.size(), &d_eqidx));
+    SX_TRY(up(C.s, d_eqidx, rp.eqidx));
+    return SX_OK;
+}
+
+int first_basic_set(BandCall &C, const HostLp &lp, const pl::RowPlan &rp, const double *x_start, pl::BasisState &bs) {
+    const int64_t m = C.m, n = C.n;
+    bs.init(n, m);
+    if (C.given) pl::basic_set_from_codes(n, m, lp.vb_in.data(), lp.cb_in.data(), lp.l.data(), lp.u.data(), bs);
+    else {
+        SX_TRY(slack_to_host(C, x_start, C.hslack)); // slack = b - A x
+        const size_t ncand = pl::basic_set_from_margins(n, m, lp.l.data(), lp.u.data(), lp.b.data(), lp.lt.data(), C.hslack.data(), bs);
+        if (C.trace) fprintf(stderr, "[sx_crossover_band] m=%lld n=%lld: %zu interior candidates, band rows %lld, dense rows %lld\n", (long long)m, (long long)n, ncand, (long long)rp.rows_band.size(), (long long)rp.rows_dense.size());
+    }
+    if (C.trace) fprintf(stderr, "[sx_crossover_band] host copies, row order and first basic set at %.1f ms\n", C.ms());
+    return SX_OK;
+}
+
+// the big blocks, allocated beside the matching, and the small per-call blocks
+int call_blocks(BandCall &C, int64_t ndr0, size_t ntracked) {
+    const int64_t m = C.m;
+    size_t free_b = 0, total_b = 0;
+    SX_HIP(hipMemGetInfo(&free_b, &total_b));
+    // (estimates before the matching: border = dense rows + up to 32 separators of ~128 rows; a twelfth of the border is
+    //  set aside by the dense LU of a guess -- 1,032 of 13,771 at config-5 size, 158 of 2,299 at the headline size)
+    const double mp_est = static_cast<double>(m) + static_cast<double>(ndr0) + 33.0 * 400.0 + 2048.0;
+    const double nb_est = static_cast<double>(ndr0) + 32.0 * 128.0 + 1024.0;
+    const double track_est = static_cast<double>(ntracked) + nb_est / 12.0;
+    const double epoch_est = std::min(std::min(20000.0, eta_columns_by_memory(free_b, mp_est)), 4.0 * (track_est + nb_est / 8.0) + 2048.0);
+    const double want = 8.0 * mp_est * (epoch_est + 2.0 + 1.5 * track_est + 712.0);
+    if (want > 2.0e9 && want < 0.6 * static_cast<double>(free_b) && !getenv("SX_BAND_NO_ARENA")) C.arena.start(C.ctx, static_cast<size_t>(want));
+    SX_TRY(C.dev.get(1, &C.d_st));
+    SX_TRY(C.dev.get(static_cast<size_t>(TB_K), &C.d_pr));
+    SX_TRY(C.dev.get(static_cast<size_t>(TB_K), &C.d_gu));
+    SX_TRY(C.dev.get(static_cast<size_t>(TB_EB) * TB_EB, &C.d_ebM));
+    C.hy.assign(static_cast<size_t>(m), 0.0);
+    return SX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- stages of an epoch
+// blocks, the epoch's row maps on the device, band triplets
+int epoch_geometry(BandCall &C, const HostLp &lp, const pl::RowPlan &rp, Epoch &E) {
+    const int64_t m1_all = static_cast<int64_t>(rp.rows_band.size());
+    const int64_t want = getenv("SX_BAND_BLOCKS") ? atoll(getenv("SX_BAND_BLOCKS")) : pl::default_block_count(m1_all);
+    pl::make_geometry(lp.csc(), rp, E.mt, want, E.g);
+    SX_TRY(E.dev.get(E.g.eqidx.size(), &E.d_eqidx));
+    SX_TRY(up(C.s, E.d_eqidx, E.g.eqidx));
+    pl::band_triplets(lp.csc(), lp.nnz, E.g, E.tri);
+    if (!sx_bandlu_supports(E.tri.kl, E.tri.ku)) {
+        sx_set_error("the basis is not a band matrix in the order of the rows (kl = %d, ku = %d after setting %lld dense rows aside)", E.tri.kl, E.tri.ku,
+                     (long long)E.g.ndr);
+        return SX_ERR_UNSUPPORTED;
+    }
+    if (C.trace) fprintf(stderr, "[sx_crossover_band] epoch %d: matching and band assembly done at %.1f ms\n", C.epochs, C.ms());
+    return SX_OK;
+}
+
+// factor B11
+int factor_band(BandCall &C, Epoch &E, bool guessed) {
+    const pl::EpochGeometry &g = E.g;
+    const int64_t m1 = g.m1, P = g.P;
+    hipStream_t s = C.s;
+    E.ph_row.assign(static_cast<size_t>(m1), -1);
+    if (m1 > 0) {
+        int32_t *d_trow = nullptr, *d_tcol = nullptr;
+        double *d_tval = nullptr;
+        DevBufs tdev;
+        SX_TRY(tdev.get(E.tri.row.size(), &d_trow));
+        SX_TRY(tdev.get(E.tri.col.size(), &d_tcol));
+        SX_TRY(tdev.get(E.tri.val.size(), &d_tval));
+        SX_TRY(up(s, d_trow, E.tri.row));
+        SX_TRY(up(s, d_tcol, E.tri.col));
+        SX_TRY(up(s, d_tval, E.tri.val));
+        SX_TRY(sx_bandlu_create_dev(C.ctx, m1, E.tri.kl, E.tri.ku, static_cast<int64_t>(E.tri.val.size()), d_trow, d_tcol, d_tval, &E.fac.lu));
+        std::vector<int32_t> rep(static_cast<size_t>(m1)), piv(static_cast<size_t>(m1));
+        SX_TRY(sx_bandlu_factor_blocks_dev(E.fac.lu, guessed ? C.tol_band_guess : C.tol_band_keep, static_cast<int>(P), P > 1 ? g.stride : m1, P > 1 ? g.RL : m1,
+                                            P > 1 ? g.RL_last : m1, &E.nrep, rep.data(), piv.data()));
+        pl::after_band_lu(E.g, E.mt, rep, piv, E.ph_row);
+    }
+    if (C.trace) fprintf(stderr, "[sx_crossover_band] epoch %d: band LU done at %.1f ms (kl=%d ku=%d, %lld blocks of %lld positions with separators of %lld, %lld columns set aside)\n", C.epochs, C.ms(), E.tri.kl, E.tri.ku, (long long)P, (long long)g.RL, (long long)g.Wsep, (long long)E.nrep);
+    return SX_OK;
+}
+
+// the border: as many columns as rows; then the eta file and B21
+int make_border(BandCall &C, const HostLp &lp, pl::BasisState &bs, Epoch &E, bool guessed) {
+    if (!pl::balance_border(C.n, E.g, E.mt, E.ph_row, guessed, bs, E.bd)) {
+        sx_set_error("the border of the basis has %lld rows and %zu columns (at most %lld rows)", (long long)(E.g.ndr + E.bd.h), E.bd.bcol.size(), (long long)pl::MAX_NB);
+        return SX_ERR_UNSUPPORTED;
+    }
+    const int64_t m1 = E.g.m1, nb = E.bd.nb(E.g), mp = m1 + nb;
+    E.nb = nb;
+    E.mp = mp;
+    // the eta file of this epoch -- allocated now because its memory doubles as the work block of the Schur complement's
+    // assembly (a block of 24 GB allocated and freed for that alone cost 0.3 s at 1e5 rows and 1.2 s at 1e6: hipFree of a
+    // touched block).  Basis changes before the basis is factored afresh: a few times the columns that can move, within
+    // 16 GB; a fresh factorisation keeps every basic variable (bordered form), so the file need not be long
+    size_t free_b = 0, total_b = 0;
+    SX_HIP(hipMemGetInfo(&free_b, &total_b));
+    const int64_t by_memory = std::max<int64_t>(64, static_cast<int64_t>(eta_columns_by_memory(free_b, static_cast<double>(mp))) - 1);
+    E.EPOCH = std::min<int64_t>(std::min<int64_t>(20000, by_memory), 4 * static_cast<int64_t>(bs.tracked.size() + static_cast<size_t>(nb) / 8) + 2048);
+    if (const char *e = getenv("SX_BAND_EPOCH")) E.EPOCH = std::max<int64_t>(16, atoll(e));
+    C.arena.reset(); // (what the last epoch held there is dead)
+    E.d_eta = static_cast<double *>(C.arena.take(sizeof(double) * static_cast<size_t>(mp) * (E.EPOCH + 1)));
+    if (!E.d_eta) SX_TRY(E.dev.get(static_cast<size_t>(mp) * (E.EPOCH + 1), &E.d_eta));
+    SX_TRY(E.dev.get(static_cast<size_t>(E.EPOCH) + 2, &E.d_eta_r));
+    // ---- B21: the dense rows' entries in the band columns, one unit entry per placeholder row
+    SxBorderOps &ops = E.ops;
+    ops.ctx = C.ctx;
+    ops.m1 = m1;
+    ops.nb = nb;
+    ops.mp = mp;
+    ops.lu = E.fac.lu;
+    ops.tiny = TB_TINY;
+    if (nb > 0) {
+        pl::HostRows b21r, b21c;
+        pl::b21_blocks(lp.csc(), E.g, E.bd, b21r, b21c);
+        SX_TRY(rows_to_dev(C, E, b21r, nb, false, ops.b21_rows));
+        SX_TRY(rows_to_dev(C, E, b21c, static_cast<int64_t>(b21c.list.size()), true, ops.b21_cols));
+    }
+    return SX_OK;
+}
+
+// the Schur complement, a block of border columns at a time: S[:, j] = (a2 - B21 B11^-1 a1) of column j
+int schur_complement(BandCall &C, pl::BasisState &bs, Epoch &E, bool guessed) {
+    const sx_matrix *A = C.A;
+    hipStream_t s = C.s;
+    SxBorderOps &ops = E.ops;
+    const int64_t nb = E.nb, mp = E.mp, m1 = E.g.m1, EPOCH = E.EPOCH;
+    int64_t nrep2 = 0;
+    if (nb > 0) {
+        {
+            size_t free_b = 0, total_b = 0;
+            SX_HIP(hipMemGetInfo(&free_b, &total_b));
+            ops.v_limit = static_cast<size_t>(std::min(4.0e9, 0.05 * static_cast<double>(free_b)) / 8.0);
+            if (getenv("SX_BAND_NO_V")) ops.v_failed = 1;
+        }
+        SX_TRY(sx_denselu_create_dev(C.ctx, nb, &E.fac.dl));
+        double *Sa = nullptr;
+        int64_t Sld = 0;
+        SX_TRY(sx_denselu_matrix(E.fac.dl, &Sa, &Sld));
+        // blocks of up to 4,096 columns (in the memory of the still empty eta file: a sparse band solve is a chain of panel steps per
+        // group of 8 columns whatever the number of groups, 250 columns a launch kept 31 of 256 CUs busy), taken in the
+        // order of the VARIABLES -- neighbours in that order live in neighbouring rows, so the 8 columns of a group share
+        // their panels -- and written to the column of S the border's own order gives them
+        const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nb, 4096), EPOCH + 1));
+        DevBufs sdev;
+        double *Wc = E.d_eta; // (the eta file is empty until the simplex starts)
+        int32_t *d_bvars = nullptr, *d_dest = nullptr;
+        SX_TRY(sdev.get(static_cast<size_t>(nb), &d_bvars));
+        SX_TRY(sdev.get(static_cast<size_t>(nb), &d_dest));
+        const std::vector<int64_t> &bcol = E.bd.bcol;
+        std::vector<int32_t> order(static_cast<size_t>(nb)), bv32(static_cast<size_t>(nb));
+        std::iota(order.begin(), order.end(), 0);
+        std::sort(order.begin(), order.end(), [&](int32_t a, int32_t bb) { return bcol[a] < bcol[bb]; });
+        for (int64_t t = 0; t < nb; ++t) bv32[t] = static_cast<int32_t>(bcol[order[t]]);
+        SX_TRY(up(s, d_bvars, bv32));
+        SX_TRY(up(s, d_dest, order));
+        C.peak_bytes = std::max(C.peak_bytes, sizeof(double) * (static_cast<size_t>(mp) * (EPOCH + 1) + static_cast<size_t>(Sld) * nb));
+        for (int64_t c0 = 0; c0 < nb; c0 += CH) {
+            const int64_t kc = std::min<int64_t>(CH, nb - c0);
+            SX_HIP(hipMemsetAsync(Wc, 0, sizeof(double) * static_cast<size_t>(mp) * kc, s));
+            hipLaunchKernelGGL(k_tb_scatter_cols, dim3(gridof(kc)), dim3(TB_WG), 0, s, kc, d_bvars + c0, C.n, A->csc_ptr, A->csc_idx, A->csc_val, E.d_eqidx, Wc, mp);
+            SX_TRY(ops.ftran(Wc, kc, true, true));
+            SX_TRY(ops.pack_v(Wc, kc, order.data() + c0)); // (the band parts B11^-1 B12 of these columns, by their windows)
+            hipLaunchKernelGGL(k_tb_copy_cols, dim3(static_cast<unsigned>(std::min<int64_t>(gridof(nb), 64)), static_cast<unsigned>(kc)), dim3(TB_WG), 0, s, nb, Wc + m1, mp,
+                               d_dest + c0, Sa, Sld);
+        }
+        SX_HIP(hipStreamSynchronize(s));
+        if (C.trace) fprintf(stderr, "[sx_crossover_band] epoch %d: Schur complement (%lld rows: %lld dense, %lld placeholders) assembled at %.1f ms\n", C.epochs, (long long)nb, (long long)E.g.ndr, (long long)E.bd.h, C.ms());
+        std::vector<int32_t> rep2(static_cast<size_t>(nb)), perm2(static_cast<size_t>(nb));
+        SX_TRY(sx_denselu_factor_dev(E.fac.dl, guessed ? C.tol_schur_guess : C.tol_schur_keep, &nrep2, rep2.data(), perm2.data()));
+        const int64_t twice = pl::after_dense_lu(C.n, E.g, E.ph_row, rep2, perm2, bs, E.bd);
+        if (twice >= 0) {
+            sx_set_error("internal: the repair of the Schur complement wants logical %lld twice", (long long)twice);
+            return SX_ERR_UNSUPPORTED;
+        }
+        SX_TRY(ops.finish_v(rep2)); // (a column that left the basis: its V column is zero, like the unit vector's that replaced it)
+        if (C.trace) {
+            std::vector<double> dg(static_cast<size_t>(nb));
+            SX_HIP(hipMemcpy2D(dg.data(), sizeof(double), Sa, sizeof(double) * (Sld + 1), sizeof(double), static_cast<size_t>(nb), hipMemcpyDeviceToHost));
+            double mn = INFINITY;
+            int64_t c2 = 0, c4 = 0, c6 = 0;
+            for (double d : dg) {
+                const double a = std::fabs(d);
+                mn = std::min(mn, a);
+                c2 += a < 1e-2;
+                c4 += a < 1e-4;
+                c6 += a < 1e-6;
+            }
+            fprintf(stderr, "[sx_crossover_band] epoch %d: Schur complement factored at %.1f ms (%lld columns set aside; smallest pivot %.2e, %lld / %lld / %lld below 1e-2 / 1e-4 / 1e-6); "
+                            "B11^-1 B12 %s: %.1f rows per border column, %.3f GB\n",
+                    C.epochs, C.ms(), (long long)nrep2, mn, (long long)c2, (long long)c4, (long long)c6, ops.v_ready ? "packed by windows" : "not kept (solve form)",
+                    static_cast<double>(ops.v_used) / static_cast<double>(nb), static_cast<double>(ops.v_used) * 8e-9);
+        }
+    }
+    ops.dl = E.fac.dl;
+    return SX_OK;
+}
+
+// B12: the border columns' entries in the band rows
+int border_blocks(BandCall &C, const HostLp &lp, Epoch &E) {
+    SxBorderOps &ops = E.ops;
+    const int64_t nb = E.nb, m1 = E.g.m1;
+    if (nb > 0 && m1 > 0) {
+        pl::HostRows b12r, b12c;
+        pl::b12_blocks(lp.csc(), E.g, E.bd, b12r, b12c);
+        SX_TRY(rows_to_dev(C, E, b12r, static_cast<int64_t>(b12r.list.size()), true, ops.b12_rows));
+        SX_TRY(rows_to_dev(C, E, b12c, nb, false, ops.b12_cols));
+        ops.work_cols = ops.v_ready ? 1 : std::max<int64_t>(1, std::min<int64_t>(128, static_cast<int64_t>(1.0e9 / (8.0 * static_cast<double>(m1)))));
+        SX_TRY(E.dev.get(static_cast<size_t>(m1) * ops.work_cols, &ops.work));
+    }
+    if (C.trace) {
+        SX_HIP(hipStreamSynchronize(C.s));
+        fprintf(stderr, "[sx_crossover_band] epoch %d: border blocks in place at %.1f ms\n", C.epochs, C.ms());
+    }
+    return SX_OK;
+}
+
+// who is where, then this epoch's blocks: positions, tableau
+int epoch_arrays(BandCall &C, pl::BasisState &bs, Epoch &E) {
+    int64_t bad = 0;
+    const int who = pl::who_is_where(C.m, E.g, E.bd, bs, E.head, E.varJ, E.n_dummy, bad);
+    if (who == 1) {
+        sx_set_error("internal: variable %lld covers two positions of the basis", (long long)bad);
+        return SX_ERR_UNSUPPORTED;
+    }
+    if (who == 2) {
+        sx_set_error("internal: %lld basic variables for %lld rows", (long long)bad, (long long)C.m);
+        return SX_ERR_UNSUPPORTED;
+    }
+    E.nJ = static_cast<int64_t>(E.varJ.size());
+    const int64_t mp = E.mp, nJ = E.nJ;
+    E.nblk = static_cast<int>(gridof(mp));
+    const int nblk = E.nblk;
+    SX_TRY(E.dev.get(static_cast<size_t>(mp), &E.d_xB));
+    SX_TRY(E.dev.get(static_cast<size_t>(mp), &E.d_lB));
+    SX_TRY(E.dev.get(static_cast<size_t>(mp), &E.d_uB));
+    SX_TRY(E.dev.get(static_cast<size_t>(mp), &E.d_cB));
+    SX_TRY(E.dev.get(static_cast<size_t>(mp), &E.d_g));
+    SX_TRY(E.dev.get(static_cast<size_t>(mp), &E.d_vec));
+    SX_TRY(E.dev.get(static_cast<size_t>(mp), &E.d_head));
+    SX_TRY(E.dev.get(static_cast<size_t>(2 * nblk), &E.d_part));
+    SX_TRY(E.dev.get(static_cast<size_t>(TB_EB) * TB_ETS, &E.d_etp));
+    SX_TRY(E.dev.get(static_cast<size_t>(nblk), &E.d_blist));
+    SX_TRY(E.dev.get(static_cast<size_t>(2 * nblk), &E.d_infpart));
+    SX_TRY(E.dev.get(static_cast<size_t>(nblk), &E.d_infoff));
+    SX_TRY(E.dev.get(static_cast<size_t>(TB_INFLIST), &E.d_inflist));
+    SX_TRY(E.dev.get(static_cast<size_t>(nblk), &E.d_rpart));
+    size_t free_b = 0, total_b = 0;
+    SX_HIP(hipMemGetInfo(&free_b, &total_b));
+    int64_t cap0 = nJ + std::max<int64_t>(512, nJ / 2); // (growing it later is an allocation, a copy and a free of GBs)
+    if (static_cast<double>(TbSlots::bytes_for(mp, cap0)) > 0.6 * static_cast<double>(free_b)) cap0 = nJ + 16;
+    if (static_cast<double>(TbSlots::bytes_for(mp, cap0)) > 0.8 * static_cast<double>(free_b)) {
+        sx_set_error("the tableau of %lld tracked columns over %lld positions does not fit the free device memory", (long long)cap0, (long long)mp);
+        return SX_ERR_NOMEM;
+    }
+    SX_TRY(E.sl.reserve(C.s, mp, cap0, 0, &C.arena));
+    C.peak_bytes = std::max(C.peak_bytes, TbSlots::bytes_for(mp, cap0) + sizeof(double) * static_cast<size_t>(mp) * (E.EPOCH + 1));
+    if (C.trace) fprintf(stderr, "[sx_crossover_band] epoch %d: tableau and position blocks allocated at %.1f ms\n", C.epochs, C.ms());
+    return SX_OK;
+}
+
+// values: non-basic and tracked columns, right-hand side; the basic variables' arrays and their values x_B = B^-1 rhs
+int values_and_rhs(BandCall &C, const HostLp &lp, pl::BasisState &bs, Epoch &E) {
+    hipStream_t s = C.s;
+    const int64_t m = C.m, n = C.n, mp = E.mp;
+    std::vector<double> &hx = bs.hx;
+    // logical of row i: s_i = b_i - (A x)_i for the tracked ones (their current value), 0 for the non-basic ones
+    SX_TRY(slack_to_host(C, hx, C.hslack));
+    std::vector<double> xN(hx);
+    for (int64_t j = 0; j < n; ++j) {
+        if (bs.vstat[j] == 1) xN[j] = 0.0;
+        else if (bs.vstat[j] == 0) {
+            const bool upb = (lp.u[j] - hx[j]) < (hx[j] - lp.l[j]);
+            double v = upb ? lp.u[j] : lp.l[j];
+            if (std::isinf(v)) v = 0.0;
+            xN[j] = v;
+            hx[j] = v;
+            bs.atup[j] = upb;
+        }
+    }
+    for (int64_t i = 0; i < m; ++i) {
+        bs.xlog[i] = 0.0;
+        if (bs.vstat[n + i] == 2) bs.xlog[i] = lp.lt[i] ? std::max(C.hslack[i], 0.0) : 0.0;
+    }
+    std::vector<double> hr;
+    SX_TRY(slack_to_host(C, xN, hr));
+    std::vector<double> rp(static_cast<size_t>(mp), 0.0); // (a placeholder's border row: 0)
+    for (int64_t i = 0; i < m; ++i) rp[E.g.eqidx[i]] = hr[i] - bs.xlog[i];
+    // ---- basic variables (a dummy -- placeholder or mirror column -- is free, costs nothing and never leaves)
+    {
+        std::vector<double> hlB(static_cast<size_t>(mp)), huB(static_cast<size_t>(mp)), hcB(static_cast<size_t>(mp));
+        std::vector<int32_t> hhead(static_cast<size_t>(mp));
+        for (int64_t p = 0; p < mp; ++p) {
+            hhead[p] = static_cast<int32_t>(E.head[p]);
+            if (E.head[p] < 0) {
+                hlB[p] = -INFINITY;
+                huB[p] = INFINITY;
+                hcB[p] = 0.0;
+                continue;
+            }
+            hlB[p] = lp.lo(E.head[p]);
+            huB[p] = lp.up(E.head[p]);
+            hcB[p] = lp.cost(E.head[p]);
+        }
+        SX_TRY(up(s, E.d_head, hhead));
+        SX_TRY(up(s, E.d_lB, hlB));
+        SX_TRY(up(s, E.d_uB, huB));
+        SX_TRY(up(s, E.d_cB, hcB));
+        SX_TRY(up(s, E.d_xB, rp));
+        SX_HIP(hipStreamSynchronize(s));
+    }
+    if (C.trace) fprintf(stderr, "[sx_crossover_band] epoch %d: right-hand side and basic variables' arrays at %.1f ms\n", C.epochs, C.ms());
+    SX_TRY(ftran_cols(C, E, E.d_xB, 1, 0, false));
+    return SX_OK;
+}
+
+// A GIVEN basis is kept as it is (tolerances of a basis the simplex has reached) -- unless its basic solution says it
+// is no basis to start from: members that are all but dependent put it far outside the bounds, and phase 1 would
+// pay for each of them pivot by pivot (15 wrong members of 1,200: 6,537 iterations against 402 from the point alone).
+// Then the same set is factored once more with the tolerances of a guess
+int given_basis_is_far(BandCall &C, const HostLp &lp, Epoch &E, bool &far) {
+    std::vector<double> t;
+    SX_TRY(down(C.s, t, E.d_xB, static_cast<size_t>(E.mp)));
+    SX_HIP(hipStreamSynchronize(C.s));
+    double worst = 0.0;
+    int64_t ninf = 0;
+    for (int64_t p = 0; p < E.mp; ++p) {
+        if (E.head[p] < 0) continue;
+        const double vi = std::max(lp.lo(E.head[p]) - t[p], t[p] - lp.up(E.head[p]));
+        if (vi > C.feas_tol) ++ninf;
+        worst = std::max(worst, vi);
+    }
+    far = worst > 1.0 || ninf > std::max<int64_t>(16, C.m / 50);
+    if (far && C.trace) fprintf(stderr, "[sx_crossover_band] the given basis puts %lld variables outside their bounds (worst %.3e): factored again with the tolerances of a guess\n", (long long)ninf, worst);
+    return SX_OK;
+}
+
+// (trace) how far the basic solution is from the point handed over (conditioning of the guessed basis)
+int trace_basic_solution(BandCall &C, const HostLp &lp, const pl::BasisState &bs, Epoch &E) {
+    const int64_t n = C.n, nb = E.nb, m1 = E.g.m1;
+    std::vector<double> t;
+    SX_TRY(down(C.s, t, E.d_xB, static_cast<size_t>(E.mp)));
+    SX_HIP(hipStreamSynchronize(C.s));
+    double devi = 0.0, worst = 0.0, dummy = 0.0;
+    int64_t ninf = 0, inf_bs = 0, inf_bl = 0, inf_border = 0, border_struct = 0;
+    for (int64_t j = 0; j < nb; ++j) border_struct += E.bd.bcol[j] >= 0 && E.bd.bcol[j] < n;
+    for (int64_t p = 0; p < E.mp; ++p) {
+        const int64_t v = E.head[p];
+        if (v < 0) {
+            if (p < m1) dummy = std::max(dummy, std::fabs(t[p]));
+            continue;
+        }
+        const double ref = v < n ? bs.hx[v] : (lp.lt[v - n] ? std::max(C.hslack[v - n], 0.0) : 0.0);
+        devi = std::max(devi, std::fabs(t[p] - ref));
+        const double vi = std::max(lp.lo(v) - t[p], t[p] - lp.up(v));
+        if (vi > C.feas_tol) {
+            ++ninf;
+            if (p >= m1) ++inf_border;
+            else if (v < n) ++inf_bs;
+            else ++inf_bl;
+        }
+        worst = std::max(worst, vi);
+    }
+    fprintf(stderr, "[sx_crossover_band] epoch %d: outside their bounds: %lld band columns, %lld band logicals, %lld border variables (the border holds %lld columns, %lld logicals)\n",
+            C.epochs, (long long)inf_bs, (long long)inf_bl, (long long)inf_border, (long long)border_struct, (long long)(nb - border_struct));
+    fprintf(stderr, "[sx_crossover_band] epoch %d: basic solution deviates from the point by at most %.3e; %lld basic variables outside their bounds (worst %.3e); "
+                    "placeholders hold at most %.1e; %.1f ms\n", C.epochs, devi, (long long)ninf, worst, dummy, C.ms());
+    return SX_OK;
+}
+
+// ---- tracked columns: their slots ...
+int load_slots(BandCall &C, const HostLp &lp, const pl::BasisState &bs, Epoch &E, int64_t s0, const std::vector<int32_t> &vars) {
+    hipStream_t s = C.s;
+    TbSlots &sl = E.sl;
+    const size_t k = vars.size();
+    if (k == 0) return SX_OK;
+    std::vector<double> vx(k), vl(k), vu(k), vc(k);
+    std::vector<int32_t> vs(k);
+    for (size_t t = 0; t < k; ++t) {
+        const int64_t v = vars[t];
+        vl[t] = lp.lo(v);
+        vu[t] = lp.up(v);
+        vc[t] = lp.cost(v);
+        vx[t] = std::min(std::max(v < C.n ? bs.hx[v] : bs.xlog[v - C.n], vl[t]), vu[t]);
+        if (vx[t] > vl[t] && vx[t] < vu[t]) vs[t] = TB_SUP;
+        else vs[t] = (vx[t] >= vu[t] && vu[t] > vl[t]) ? TB_UPP : TB_LOW;
+    }
+    SX_HIP(hipMemcpyAsync(sl.varJ + s0, vars.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, s));
+    SX_HIP(hipMemcpyAsync(sl.xJ + s0, vx.data(), sizeof(double) * k, hipMemcpyHostToDevice, s));
+    SX_HIP(hipMemcpyAsync(sl.lJ + s0, vl.data(), sizeof(double) * k, hipMemcpyHostToDevice, s));
+    SX_HIP(hipMemcpyAsync(sl.uJ + s0, vu.data(), sizeof(double) * k, hipMemcpyHostToDevice, s));
+    SX_HIP(hipMemcpyAsync(sl.cJ + s0, vc.data(), sizeof(double) * k, hipMemcpyHostToDevice, s));
+    SX_HIP(hipMemcpyAsync(sl.statJ + s0, vs.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, s));
+    SX_HIP(hipStreamSynchronize(s)); // (the staging vectors go out of scope)
+    return SX_OK;
+}
+// ... and their tableau columns T[:, s0 .. s0 + k) = B^-1 a_j with their reduced costs
+int build_cols(BandCall &C, Epoch &E, int64_t s0, int64_t k, int64_t n_eta_now) {
+    if (k == 0) return SX_OK;
+    const sx_matrix *A = C.A;
+    hipStream_t s = C.s;
+    TbSlots &sl = E.sl;
+    const int64_t mp = E.mp;
+    double *W = sl.T + static_cast<size_t>(s0) * mp;
+    SX_HIP(hipMemsetAsync(W, 0, sizeof(double) * static_cast<size_t>(mp) * k, s));
+    hipLaunchKernelGGL(k_tb_scatter_cols, dim3(gridof(k)), dim3(TB_WG), 0, s, k, sl.varJ + s0, C.n, A->csc_ptr, A->csc_idx, A->csc_val, E.d_eqidx, W, mp);
+    SX_TRY(ftran_cols(C, E, W, k, n_eta_now, true));
+    hipLaunchKernelGGL(k_tb_drop, dim3(gridcap(mp * k)), dim3(TB_WG), 0, s, mp * k, W, 10.0 * TB_DROP);
+    // reduced costs of the new columns under the current basis: d = c_J - c_B^T T
+    hipLaunchKernelGGL(k_tb_coldot, dim3(static_cast<unsigned>(k)), dim3(TB_WG), 0, s, mp, W, E.d_cB, sl.cJ + s0, sl.dJ + s0);
+    SX_HIP(hipGetLastError());
+    return SX_OK;
+}
+
+// the first tableau columns of the epoch and the state the device starts from
+int tableau_columns(BandCall &C, const HostLp &lp, const pl::BasisState &bs, Epoch &E) {
+    hipStream_t s = C.s;
+    SX_TRY(load_slots(C, lp, bs, E, 0, E.varJ));
+    SX_TRY(build_cols(C, E, 0, E.nJ, 0));
+    if (C.trace) {
+        SX_HIP(hipStreamSynchronize(s));
+        fprintf(stderr, "[sx_crossover_band] epoch %d: tableau columns (FTRAN of %lld) done at %.1f ms\n", C.epochs, (long long)E.nJ, C.ms());
+    }
+    E.hst = TbState{};
+    E.hst.max_iter = C.max_iter - C.tot_iters;
+    E.hst.cap_eta = E.EPOCH;
+    E.hst.feas_tol = C.feas_tol;
+    E.hst.opt_tol = C.opt_tol;
+    SX_HIP(hipMemcpyAsync(C.d_st, &E.hst, sizeof(E.hst), hipMemcpyHostToDevice, s));
+    SX_HIP(hipStreamSynchronize(s));
+    if (C.trace)
+        fprintf(stderr, "[sx_crossover_band] epoch %d: %lld positions (%lld band + %lld border, %lld dummies), %lld tracked columns (tableau capacity %lld = %.2f GB, "
+                        "eta file %lld = %.2f GB); %.1f ms so far\n", C.epochs, (long long)E.mp, (long long)E.g.m1, (long long)E.nb, (long long)E.n_dummy, (long long)E.nJ,
+                (long long)E.sl.cap, static_cast<double>(E.mp) * E.sl.cap * 8e-9, (long long)E.EPOCH, static_cast<double>(E.mp) * (E.EPOCH + 1) * 8e-9, C.ms());
+    return SX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the simplex on the tracked columns
+void one_pivot(BandCall &C, Epoch &E) {
+    hipStream_t s = C.s;
+    TbSlots &sl = E.sl;
+    TbState *d_st = C.d_st;
+    const int64_t mp = E.mp, nJ = E.nJ;
+    const int nblk = E.nblk;
+    const TbPend pend{sl.vbuf, C.d_pr, sl.s0, sl.sbase, sl.cap};
+    hipLaunchKernelGGL(k_tb_infeas, dim3(nblk), dim3(TB_WG), 0, s, mp, E.d_xB, E.d_lB, E.d_uB, d_st, E.d_g, E.d_infpart);
+    hipLaunchKernelGGL(k_tb_phase, dim3(1), dim3(TB_WG), 0, s, nblk, E.d_infpart, d_st, E.d_infoff);
+    hipLaunchKernelGGL(k_tb_inflist, dim3(nblk), dim3(TB_WG), 0, s, mp, E.d_g, E.d_infpart, E.d_infoff, d_st, E.d_inflist);
+    hipLaunchKernelGGL(k_tb_gu, dim3(TB_K), dim3(TB_WG), 0, s, mp, nblk, E.d_eta, E.d_g, E.d_inflist, d_st, pend, C.d_gu);
+    hipLaunchKernelGGL(k_tb_price1, dim3(static_cast<unsigned>(nJ)), dim3(TB_WG), 0, s, mp, nblk, sl.T, E.d_g, E.d_inflist, d_st, pend, C.d_gu, sl.d1);
+    hipLaunchKernelGGL(k_tb_select, dim3(1), dim3(TB_WG), 0, s, nJ, sl.dJ, sl.d1, sl.statJ, sl.xJ, sl.lJ, sl.uJ, d_st);
+    hipLaunchKernelGGL(k_tb_ratio1, dim3(nblk), dim3(TB_WG), 0, s, mp, sl.T, E.d_xB, E.d_lB, E.d_uB, d_st, E.d_eta, E.d_part, pend);
+    hipLaunchKernelGGL(k_tb_tmax, dim3(1), dim3(TB_WG), 0, s, nblk, E.d_part, d_st, E.d_blist);
+    hipLaunchKernelGGL(k_tb_ratio, dim3(nblk), dim3(TB_WG), 0, s, mp, E.d_xB, E.d_lB, E.d_uB, d_st, E.d_eta, E.d_rpart);
+    hipLaunchKernelGGL(k_tb_decide, dim3(1), dim3(TB_WG), 0, s, nblk, E.d_rpart, sl.xJ, sl.lJ, sl.uJ, sl.statJ, d_st);
+    hipLaunchKernelGGL(k_tb_rowcopy, dim3(gridof(nJ)), dim3(TB_WG), 0, s, mp, nJ, sl.T, E.d_eta, d_st, pend, sl.rowbuf);
+    hipLaunchKernelGGL(k_tb_update, dim3(static_cast<unsigned>(std::min(nblk, 64))), dim3(TB_WG), 0, s, mp, E.d_xB, E.d_eta, d_st, E.d_blist);
+    hipLaunchKernelGGL(k_tb_post, dim3(1), dim3(TB_WG), 0, s, nJ, sl.dJ, sl.rowbuf, E.d_head, E.d_xB, E.d_lB, E.d_uB, E.d_cB, sl.varJ, sl.xJ, sl.lJ, sl.uJ,
+                       sl.cJ, sl.statJ, E.d_eta_r, d_st, sl.vbuf, sl.cap, C.d_pr, sl.s0, sl.sbase);
+}
+void fold(BandCall &C, Epoch &E) { // applies the pending batch when it is nearly full, or when the run has stopped
+    hipStream_t s = C.s;
+    TbSlots &sl = E.sl;
+    const int64_t mp = E.mp, nJ = E.nJ;
+    const TbPend pend{sl.vbuf, C.d_pr, sl.s0, sl.sbase, sl.cap};
+    hipLaunchKernelGGL(k_tb_fold_begin, dim3(1), dim3(1), 0, s, C.d_st, 16);
+    hipLaunchKernelGGL(k_tb_fold, dim3(static_cast<unsigned>(std::min(E.nblk, 128)), static_cast<unsigned>((nJ + TB_FJ - 1) / TB_FJ)), dim3(TB_WG), 0, s,
+                       mp, nJ, sl.T, E.d_eta, C.d_st, pend);
+    hipLaunchKernelGGL(k_tb_fold_end, dim3(gridof(nJ)), dim3(TB_WG), 0, s, nJ, C.d_st, sl.s0, sl.sbase);
+    hipLaunchKernelGGL(k_tb_fold_done, dim3(1), dim3(1), 0, s, C.d_st);
+}
+// pivots in batches of 16 until the device stops: E.hst.status != 0
+int run_pivots(BandCall &C, Epoch &E) {
+    hipStream_t s = C.s;
+    TbState &hst = E.hst;
+    if (E.nJ > 0) {
+        for (;;) {
+            for (int k = 0; k < 16; ++k) one_pivot(C, E);
+            fold(C, E);
+            SX_HIP(hipMemcpyAsync(&hst, C.d_st, sizeof(hst), hipMemcpyDeviceToHost, s));
+            SX_HIP(hipStreamSynchronize(s));
+            SX_HIP(hipGetLastError());
+            if (hst.status != 0) break;
+        }
+    } else { // nothing tracked: only the state of the basic variables decides the phase
+        hipLaunchKernelGGL(k_tb_infeas, dim3(E.nblk), dim3(TB_WG), 0, s, E.mp, E.d_xB, E.d_lB, E.d_uB, C.d_st, E.d_g, E.d_infpart);
+        hipLaunchKernelGGL(k_tb_phase, dim3(1), dim3(TB_WG), 0, s, E.nblk, E.d_infpart, C.d_st, E.d_infoff);
+        SX_HIP(hipMemcpyAsync(&hst, C.d_st, sizeof(hst), hipMemcpyDeviceToHost, s));
+        SX_HIP(hipStreamSynchronize(s));
+        hst.status = 1;
+    }
+    return SX_OK;
+}
+// no tracked column prices out: duals, then the reduced costs of every other column (E.hrc) and who is where now
+// (bs.vstat).  In phase 1 the cost is the infeasibility's (g on the basic variables, nothing elsewhere)
+int price_all(BandCall &C, pl::BasisState &bs, Epoch &E, int rounds, bool ph1) {
+    hipStream_t s = C.s;
+    const int64_t m = C.m, n = C.n, mp = E.mp;
+    const TbState &hst = E.hst;
+    SX_HIP(hipMemcpyAsync(E.d_vec, ph1 ? E.d_g : E.d_cB, sizeof(double) * static_cast<size_t>(mp), hipMemcpyDeviceToDevice, s));
+    const int ets = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(TB_ETS, mp / 8192)));
+    for (int64_t hi = hst.n_eta; hi > 0; hi -= TB_EB) { // blocks of TB_EB etas, the youngest first
+        const int64_t k0 = std::max<int64_t>(0, hi - TB_EB);
+        const int K = static_cast<int>(hi - k0);
+        hipLaunchKernelGGL(k_tb_etat_dots, dim3(static_cast<unsigned>(ets), static_cast<unsigned>(K)), dim3(TB_WG), 0, s, mp, E.d_vec, E.d_eta, E.d_eta_r, k0, E.d_etp);
+        hipLaunchKernelGGL(k_tb_etat_solve, dim3(1), dim3(64), 0, s, mp, ets, K, E.d_vec, E.d_eta, E.d_eta_r, k0, E.d_etp);
+    }
+    SX_TRY(E.ops.btran(E.d_vec)); // B_aug^T y = v: position space in, row space out
+    std::vector<double> yeq;
+    SX_TRY(down(s, yeq, E.d_vec, static_cast<size_t>(mp)));
+    SX_HIP(hipStreamSynchronize(s));
+    if (C.trace) fprintf(stderr, "[sx_crossover_band]   round %d: duals (eta file of %lld, transposed solves) by %.1f ms\n", rounds, (long long)hst.n_eta, C.ms());
+    for (int64_t i = 0; i < m; ++i) C.hy[i] = yeq[E.g.eqidx[i]];
+    // reduced costs of all structural columns with these duals (the K1 walk): rc = c' - A^T y
+    SX_HIP(hipMemcpyAsync(C.d_tmpm, C.hy.data(), sizeof(double) * static_cast<size_t>(m), hipMemcpyHostToDevice, s));
+    const double *cost = C.c;
+    if (ph1) {
+        SX_HIP(hipMemsetAsync(C.d_tmpn, 0, sizeof(double) * static_cast<size_t>(n), s));
+        cost = C.d_tmpn;
+    }
+    SX_TRY(sx_score_columns_dev(C.ctx, C.A, C.d_tmpm, cost, nullptr, nullptr, nullptr, 0.0, C.d_rc, nullptr));
+    SX_TRY(down(s, E.hrc, C.d_rc, static_cast<size_t>(n)));
+    // who is where now
+    std::vector<int32_t> hh, hvarJ, hstatJ;
+    SX_TRY(down(s, hh, E.d_head, static_cast<size_t>(mp)));
+    SX_TRY(down(s, hvarJ, E.sl.varJ, static_cast<size_t>(E.nJ)));
+    SX_TRY(down(s, hstatJ, E.sl.statJ, static_cast<size_t>(E.nJ)));
+    SX_HIP(hipStreamSynchronize(s));
+    if (C.trace) fprintf(stderr, "[sx_crossover_band]   round %d: reduced costs by %.1f ms\n", rounds, C.ms());
+    vstat_from_device(hh, hvarJ, nullptr, bs.vstat);
+    return SX_OK;
+}
+// the columns outside the tableau that price out under E.hrc / C.hy, the worst first (ties by variable)
+void violators(const BandCall &C, const HostLp &lp, const pl::BasisState &bs, const Epoch &E, std::vector<std::pair<double, int32_t>> &viol) {
+    const int64_t m = C.m, n = C.n;
+    const double opt_tol = C.opt_tol;
+    viol.clear();
+    for (int64_t j = 0; j < n; ++j) {
+        if (bs.vstat[j] != 0 || lp.l[j] == lp.u[j]) continue;
+        const double d = E.hrc[j];
+        // a free column rests at 0 and may move either way (it loads as TB_SUP): both signs price
+        const bool free_col = std::isinf(lp.l[j]) && std::isinf(lp.u[j]);
+        if (free_col ? std::fabs(d) > opt_tol : (bs.atup[j] ? d > opt_tol : d < -opt_tol)) viol.emplace_back(std::fabs(d), static_cast<int32_t>(j));
+    }
+    for (int64_t i = 0; i < m; ++i) { // non-basic logicals sit at 0: reduced cost -y_i, only '<' rows may move (up)
+        if (bs.vstat[n + i] != 0 || !lp.lt[i]) continue;
+        const double d = -C.hy[i];
+        if (d < -opt_tol) viol.emplace_back(std::fabs(d), static_cast<int32_t>(n + i));
+    }
+}
+// the (up to 2,048) worst violators join the tableau
+int bring_in(BandCall &C, const HostLp &lp, pl::BasisState &bs, Epoch &E, std::vector<std::pair<double, int32_t>> &viol, int rounds) {
+    hipStream_t s = C.s;
+    TbState &hst = E.hst;
+    const int64_t mp = E.mp;
+    std::sort(viol.begin(), viol.end(), [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &bb) { return a.first > bb.first || (a.first == bb.first && a.second < bb.second); });
+    const int64_t take = std::min<int64_t>(static_cast<int64_t>(viol.size()), 2048);
+    if (E.nJ + take > E.sl.cap) { // (nothing is pending here: the run stopped, its batch was folded)
+        const int rc_ = E.sl.reserve(s, mp, E.nJ + take + std::max<int64_t>(512, E.nJ / 2), E.nJ);
+        if (rc_ != SX_OK) return rc_;
+        C.peak_bytes = std::max(C.peak_bytes, 2 * TbSlots::bytes_for(mp, E.nJ) + sizeof(double) * static_cast<size_t>(mp) * (E.EPOCH + 1));
+    }
+    std::vector<int32_t> add(static_cast<size_t>(take));
+    for (int64_t t = 0; t < take; ++t) add[t] = viol[t].second;
+    std::sort(add.begin(), add.end());
+    for (int32_t v : add)
+        if (v >= C.n) bs.xlog[v - C.n] = 0.0;
+    SX_TRY(load_slots(C, lp, bs, E, E.nJ, add));
+    SX_TRY(build_cols(C, E, E.nJ, take, hst.n_eta));
+    E.nJ += take;
+    C.added_total += take;
+    hst.status = 0;
+    SX_HIP(hipMemcpyAsync(C.d_st, &hst, sizeof(hst), hipMemcpyHostToDevice, s)); // (status only changed; counters as read)
+    SX_HIP(hipStreamSynchronize(s));
+    if (C.trace) fprintf(stderr, "[sx_crossover_band]   round %d: %lld columns brought into the tableau by %.1f ms\n", rounds, (long long)take, C.ms());
+    return SX_OK;
+}
+// rounds of "pivot until no tracked column prices out, then price all the others and bring the violators in" until the
+// epoch ends: optimal or infeasible over all columns, unbounded, out of iterations, numerical trouble -- or the eta file
+// is full (E.restart)
+int simplex_rounds(BandCall &C, const HostLp &lp, pl::BasisState &bs, Epoch &E) {
+    TbState &hst = E.hst;
+    int rounds = 0;
+    std::vector<std::pair<double, int32_t>> viol;
+    for (;;) {
+        ++rounds;
+        SX_TRY(run_pivots(C, E));
+        if (C.trace)
+            fprintf(stderr, "[sx_crossover_band]   round %d: status %d after %lld iterations (%lld pivots, %lld flips, %lld of no length), phase %d, %d "
+                            "infeasible (sum %.3e), %.1f ms so far\n", rounds, hst.status, hst.iters, hst.pivots, hst.flips, hst.degen, hst.phase,
+                    hst.n_inf, hst.sum_inf, C.ms());
+        if (hst.status == 3 && hst.n_eta >= hst.cap_eta && C.tot_iters + hst.iters < C.max_iter) {
+            E.restart = true; // the eta file is full: factor the basis afresh
+            break;
+        }
+        if (hst.status != 1) break;
+        const bool ph1 = hst.phase == 1;
+        SX_TRY(price_all(C, bs, E, rounds, ph1));
+        violators(C, lp, bs, E, viol);
+        if (C.trace) fprintf(stderr, "[sx_crossover_band]   round %d (%s): %zu columns outside the tableau price out\n", rounds, ph1 ? "phase 1" : "phase 2", viol.size());
+        if (viol.empty()) {
+            if (ph1) hst.status = 101; // infeasible: no column anywhere reduces the infeasibility
+            break;
+        }
+        SX_TRY(bring_in(C, lp, bs, E, viol, rounds));
+    }
+    return SX_OK;
+}
+
+// the epoch's end state -> host: the basic set, the tracked columns and the point as the device left them
+int end_state(BandCall &C, const HostLp &lp, pl::BasisState &bs, Epoch &E) {
+    hipStream_t s = C.s;
+    const int64_t n = C.n, mp = E.mp, nJ = E.nJ;
+    SX_TRY(down(s, E.hh, E.d_head, static_cast<size_t>(mp)));
+    SX_TRY(down(s, E.hxb, E.d_xB, static_cast<size_t>(mp)));
+    SX_TRY(down(s, E.hvarJ, E.sl.varJ, static_cast<size_t>(nJ)));
+    SX_TRY(down(s, E.hstatJ, E.sl.statJ, static_cast<size_t>(nJ)));
+    SX_TRY(down(s, E.hxJ, E.sl.xJ, static_cast<size_t>(nJ)));
+    SX_HIP(hipStreamSynchronize(s));
+    C.tot_iters += E.hst.iters;
+    C.tot_pivots += E.hst.pivots;
+    C.tot_flips += E.hst.flips;
+    C.tot_degen += E.hst.degen;
+    vstat_from_device(E.hh, E.hvarJ, &E.hstatJ, bs.vstat);
+    C.viol_max = basic_values_to_point(lp, E.hh, E.hxb, bs.hx);
+    std::fill(bs.is_basic.begin(), bs.is_basic.end(), 0);
+    bs.prev_pos.assign(static_cast<size_t>(E.g.m1_all), -1);
+    for (int64_t p = 0; p < mp; ++p) {
+        const int64_t v = E.hh[p];
+        if (v < 0) continue;
+        bs.is_basic[v] = 1;
+        if (p < E.g.m1 && v == E.head[p] && E.g.old_of_new[p] >= 0) bs.prev_pos[E.g.old_of_new[p]] = v;
+    }
+    bs.tracked.clear();
+    for (int64_t t = 0; t < nJ; ++t) {
+        const int64_t v = E.hvarJ[t];
+        bs.tracked.push_back(static_cast<int32_t>(v));
+        if (v < n) {
+            bs.hx[v] = E.hxJ[t];
+            bs.atup[v] = E.hstatJ[t] == TB_UPP;
+        }
+    }
+    C.final_status = E.hst.status;
+    return SX_OK;
+}
+
+// The vertex against A itself before it is called optimal: x_B was only ever updated, y came through the eta
+// file -- row residuals of x (one K2 walk) and the reduced costs of the basic columns (they are in E.hrc).
+// ok = false: beyond the tolerances (the driver factors the current basis afresh and goes on from there, twice at most)
+int check_vertex(BandCall &C, const HostLp &lp, pl::BasisState &bs, Epoch &E, bool &ok) {
+    hipStream_t s = C.s;
+    const int64_t m = C.m, n = C.n, mp = E.mp;
+    SX_TRY(slack_to_host(C, bs.hx, C.hslack));
+    C.resid_max = row_residual(lp, C.hslack);
+    if (C.resid_max > 1e-11) {
+        // one step of iterative refinement with the factors at hand: B delta = b - A x - s (s: the logicals'
+        // values), x_B += delta -- what thousands of updates x_B -= theta alpha left behind goes at once
+        std::vector<double> slog(static_cast<size_t>(m), 0.0), rr(static_cast<size_t>(mp), 0.0), delta;
+        for (int64_t p = 0; p < mp; ++p)
+            if (E.hh[p] >= n) slog[E.hh[p] - n] = E.hxb[p];
+        for (int64_t t = 0; t < E.nJ; ++t)
+            if (E.hvarJ[t] >= n) slog[E.hvarJ[t] - n] = E.hxJ[t];
+        for (int64_t i = 0; i < m; ++i) rr[E.g.eqidx[i]] = C.hslack[i] - slog[i];
+        SX_TRY(up(s, E.d_vec, rr));
+        SX_TRY(ftran_cols(C, E, E.d_vec, 1, E.hst.n_eta, false));
+        SX_TRY(down(s, delta, E.d_vec, static_cast<size_t>(mp)));
+        SX_HIP(hipStreamSynchronize(s));
+        for (int64_t p = 0; p < mp; ++p)
+            if (E.hh[p] >= 0) E.hxb[p] += delta[p];
+        C.viol_max = basic_values_to_point(lp, E.hh, E.hxb, bs.hx);
+        SX_TRY(slack_to_host(C, bs.hx, C.hslack));
+        const double before = C.resid_max;
+        C.resid_max = row_residual(lp, C.hslack);
+        if (C.trace) fprintf(stderr, "[sx_crossover_band] refinement of x_B: row residual %.2e -> %.2e (relative), bound violation %.2e\n", before, C.resid_max, C.viol_max);
+    }
+    double rc_basic = 0.0;
+    if (static_cast<int64_t>(E.hrc.size()) == n)
+        for (int64_t j = 0; j < n; ++j)
+            if (bs.vstat[j] == 1) rc_basic = std::max(rc_basic, std::fabs(E.hrc[j]) / (1.0 + std::fabs(lp.c[j])));
+    if (C.trace) fprintf(stderr, "[sx_crossover_band] check of the vertex: row residual %.2e (relative), reduced costs of basic columns %.2e\n", C.resid_max, rc_basic);
+    ok = !(C.resid_max > 10.0 * C.feas_tol || rc_basic > 10.0 * C.opt_tol || C.viol_max > 10.0 * C.feas_tol);
+    return SX_OK;
+}
+
+int outputs(BandCall &C, const HostLp &lp, const pl::BasisState &bs, double *x_out, double *y_out, int8_t *vbasis_out, int8_t *cbasis_out,
+            sx_simplex_result *result) {
+    hipStream_t s = C.s;
+    const int64_t m = C.m, n = C.n;
+    std::vector<int8_t> vb(static_cast<size_t>(n)), cb(static_cast<size_t>(m), -1);
+    // (a non-basic free column sits at no bound: -3, the code it is read with on entry)
+    for (int64_t j = 0; j < n; ++j)
+        vb[j] = bs.vstat[j] == 1 ? 0 : ((bs.vstat[j] == 3 || (std::isinf(lp.l[j]) && std::isinf(lp.u[j]))) ? -3 : (bs.atup[j] ? -2 : -1));
+    for (int64_t i = 0; i < m; ++i)
+        if (bs.vstat[n + i] == 1) cb[i] = 0;
+    double obj = 0.0;
+    for (int64_t j = 0; j < n; ++j) obj += lp.c[j] * bs.hx[j];
+    if (x_out) SX_HIP(hipMemcpyAsync(x_out, bs.hx.data(), sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, s));
+    if (y_out) SX_HIP(hipMemcpyAsync(y_out, C.hy.data(), sizeof(double) * static_cast<size_t>(m), hipMemcpyHostToDevice, s));
+    if (vbasis_out) SX_HIP(hipMemcpyAsync(vbasis_out, vb.data(), static_cast<size_t>(n), hipMemcpyHostToDevice, s));
+    if (cbasis_out) SX_HIP(hipMemcpyAsync(cbasis_out, cb.data(), static_cast<size_t>(m), hipMemcpyHostToDevice, s));
+    SX_HIP(hipStreamSynchronize(s));
+    result->status = C.final_status == 1 ? 0 : (C.final_status == 101 ? 1 : C.final_status);
+    result->iters = C.tot_iters;
+    result->phase1_iters = C.added_total;
+    result->warm_start_used = C.given ? 1 : 0;
+    result->obj = obj;
+    result->max_violation = std::max(C.viol_max > 0 ? C.viol_max : 0.0, C.resid_max);
+    if (C.trace)
+        fprintf(stderr, "[sx_crossover_band] done: status %lld, %lld iterations (%lld pivots, %lld flips, %lld of no length) in %d epochs, %lld columns added by "
+                        "pricing, objective %.12e, max violation %.2e, largest blocks %.2f GB, %.1f ms\n", (long long)result->status, C.tot_iters, C.tot_pivots, C.tot_flips,
+                C.tot_degen, C.epochs, (long long)C.added_total, obj, result->max_violation, static_cast<double>(C.peak_bytes) * 1e-9, C.ms());
+    return SX_OK;
+}
 
 // One entry for the three ways the sparse crossover is started: from the first-order point alone (vbasis_in == NULL: the
 // basis is guessed from the margins), or from a given basis (the reference's warm-started final solve,
-// lp_methods/algorithms.py:69-74; sx_crossover_band_dev passes NULL).
-namespace {
+// lp_methods/algorithms.py:69-74; sx_crossover_band_dev passes NULL).  The control flow and nothing else: every stage is a
+// function above, the host set-up between them is sx_band_plan.h.
 int crossover_band_impl(sx_ctx *ctx, const sx_matrix *A, const double *b, const double *c, const double *l,
                         const double *u, const uint8_t *row_is_lt, const double *x_start, const int8_t *vbasis_in,
                         const int8_t *cbasis_in, int64_t max_iter, double feas_tol, double opt_tol, double *x_out,
@@ -1106,1257 +2046,96 @@ int crossover_band_impl(sx_ctx *ctx, const sx_matrix *A, const double *b, const 
     SX_REQUIRE(A && b && c && l && u && x_start && result, "NULL argument");
     SX_REQUIRE((vbasis_in == nullptr) == (cbasis_in == nullptr), "vbasis_in and cbasis_in come together");
     SX_REQUIRE(A->csr_ptr && A->csc_ptr, "the sparse crossover needs both layouts of A");
-    const int64_t m = A->m, n = A->n;
-    SX_REQUIRE(m > 0 && n > 0 && m + n < 2000000000LL, "problem size");
-    const bool trace = getenv("SX_SPX_TRACE") != nullptr;
-    hipStream_t s = ctx->stream;
-    auto now = []() {
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-    };
-    const double t_begin = now();
+    SX_REQUIRE(A->m > 0 && A->n > 0 && A->m + A->n < 2000000000LL, "problem size");
+    BandCall C;
+    C.ctx = ctx;
+    C.A = A;
+    C.b = b;
+    C.c = c;
+    C.s = ctx->stream;
+    C.trace = getenv("SX_SPX_TRACE") != nullptr;
+    C.given = vbasis_in != nullptr;
+    C.t_begin = BandCall::now();
+    C.m = A->m;
+    C.n = A->n;
+    C.max_iter = max_iter > 0 ? max_iter : 50 * (A->m + A->n);
+    C.feas_tol = feas_tol > 0 ? feas_tol : 1e-7;
+    C.opt_tol = opt_tol > 0 ? opt_tol : 1e-7;
+    if (getenv("SX_BAND_PIVTOL_B")) C.tol_band_guess = atof(getenv("SX_BAND_PIVTOL_B"));
+    if (getenv("SX_BAND_PIVTOL_S")) C.tol_schur_guess = atof(getenv("SX_BAND_PIVTOL_S"));
     *result = sx_simplex_result{};
     result->status = 4;
-    const int64_t NV = n + m;
-    if (max_iter <= 0) max_iter = 50 * (m + n);
-    if (!(feas_tol > 0)) feas_tol = 1e-7;
-    if (!(opt_tol > 0)) opt_tol = 1e-7;
-    DevBufs dev; // lives as long as the call
+    // ---- 1. probe shortcut
     if (probe_only && !vbasis_in) {
-        // the question "would the band LU take the matched basis?" has a sufficient answer in the matrix alone: no column of
-        // A is taller (over the rows that are not dense) than a band the LU takes, so no basis is.  One kernel instead of the
-        // host copies, the row order and the matching (18 ms at 1e5 rows); a matrix that fails it gets the full answer below
-        const double avg_row_q = static_cast<double>(A->nnz) / static_cast<double>(m);
-        const int64_t dense_thr_q = std::max<int64_t>(24, static_cast<int64_t>(6.0 * avg_row_q));
-        int *d_q = nullptr;
-        SX_TRY(dev.get(2, &d_q));
-        SX_HIP(hipMemsetAsync(d_q, 0, 2 * sizeof(int), s));
-        hipLaunchKernelGGL(k_tb_colspan, dim3(gridof(std::max(m, n))), dim3(TB_WG), 0, s, m, n, A->csc_ptr, A->csc_idx, A->csr_ptr, dense_thr_q, d_q);
-        int hq[2] = {0, 0};
-        SX_HIP(hipMemcpyAsync(hq, d_q, sizeof(hq), hipMemcpyDeviceToHost, s));
-        SX_HIP(hipStreamSynchronize(s));
-        if (trace) fprintf(stderr, "[sx_crossover_band] probe: tallest column %d rows outside the %d dense rows\n", hq[0], hq[1]);
-        if (hq[1] <= 16384 / 2 && sx_bandlu_supports(hq[0], hq[0])) {
+        bool taken = false;
+        SX_TRY(probe_shortcut(C, taken));
+        if (taken) {
             result->status = 0;
             return SX_OK;
         }
     }
-    // ------------------------------------------------------------------ host copies (once)
-    std::vector<int64_t> cptr, rptr;
-    std::vector<int32_t> cidx;
-    std::vector<double> cval, hb, hc, hl, hu, hx, hslack;
-    std::vector<uint8_t> hlt(static_cast<size_t>(m), 0);
-    std::vector<int8_t> vb_in, cb_in;
-    SX_TRY(down(s, cptr, A->csc_ptr, static_cast<size_t>(n) + 1));
-    SX_TRY(down(s, rptr, A->csr_ptr, static_cast<size_t>(m) + 1));
-    SX_TRY(down(s, cidx, A->csc_idx, static_cast<size_t>(A->nnz)));
-    SX_TRY(down(s, cval, A->csc_val, static_cast<size_t>(A->nnz)));
-    SX_TRY(down(s, hb, b, static_cast<size_t>(m)));
-    SX_TRY(down(s, hc, c, static_cast<size_t>(n)));
-    SX_TRY(down(s, hl, l, static_cast<size_t>(n)));
-    SX_TRY(down(s, hu, u, static_cast<size_t>(n)));
-    SX_TRY(down(s, hx, x_start, static_cast<size_t>(n)));
-    if (row_is_lt) SX_HIP(hipMemcpyAsync(hlt.data(), row_is_lt, static_cast<size_t>(m), hipMemcpyDeviceToHost, s));
-    if (vbasis_in) {
-        SX_TRY(down(s, vb_in, vbasis_in, static_cast<size_t>(n)));
-        SX_TRY(down(s, cb_in, cbasis_in, static_cast<size_t>(m)));
-    }
-    double *d_tmpm = nullptr, *d_tmpn = nullptr, *d_rc = nullptr;
-    SX_TRY(dev.get(static_cast<size_t>(m), &d_tmpm));
-    SX_TRY(dev.get(static_cast<size_t>(n), &d_tmpn));
-    SX_TRY(dev.get(static_cast<size_t>(n), &d_rc));
-    SX_HIP(hipStreamSynchronize(s));
-    for (int64_t j = 0; j < n; ++j) hx[j] = std::min(std::max(hx[j], hl[j]), hu[j]);
-    auto var_lo = [&](int64_t v) { return v < n ? hl[v] : 0.0; };
-    auto var_up = [&](int64_t v) { return v < n ? hu[v] : (hlt[v - n] ? INFINITY : 0.0); };
-    auto var_cost = [&](int64_t v) { return v < n ? hc[v] : 0.0; };
-    // ------------------------------------------------------------------ dense rows, band rows (once)
-    const double avg_row = static_cast<double>(A->nnz) / static_cast<double>(m);
-    const int64_t dense_thr = std::max<int64_t>(24, static_cast<int64_t>(6.0 * avg_row));
-    std::vector<int32_t> eqidx(static_cast<size_t>(m)), rows_band, rows_dense;
-    for (int64_t i = 0; i < m; ++i) {
-        if (rptr[i + 1] - rptr[i] > dense_thr) rows_dense.push_back(static_cast<int32_t>(i));
-        else rows_band.push_back(static_cast<int32_t>(i));
-    }
-    const int64_t m1 = static_cast<int64_t>(rows_band.size()), ndr = static_cast<int64_t>(rows_dense.size());
-    constexpr int64_t MAX_NB = 16384; // rows of the Schur complement the dense LU takes
-    if (ndr > MAX_NB) {
-        sx_set_error("%lld rows with more than %lld entries: the border of the basis would pass the dense LU's %lld rows", (long long)ndr,
-                     (long long)dense_thr, (long long)MAX_NB);
-        return SX_ERR_UNSUPPORTED;
-    }
-    std::vector<int32_t> rowb(static_cast<size_t>(m), -1);
-    // ---- the order of the band rows.  Natural order first (staged models are written stage after stage); when
-    // that leaves some column taller than a band can be, a Cuthill-McKee order of the rows (breadth first over
-    // "shares a column with", from a far end found by one extra sweep) -- rows of a model that was shuffled, or
-    // written variable by variable, fall back into stages.
-    {
-        auto tallest = [&](const std::vector<int32_t> &order) {
-            std::vector<int32_t> where(static_cast<size_t>(m), -1);
-            for (size_t k = 0; k < order.size(); ++k) where[order[k]] = static_cast<int32_t>(k);
-            int32_t worst = 0;
-            for (int64_t j = 0; j < n; ++j) {
-                int32_t lo = INT32_MAX, hi = -1;
-                for (int64_t k = cptr[j]; k < cptr[j + 1]; ++k) {
-                    const int32_t ib = where[cidx[k]];
-                    if (ib >= 0) {
-                        lo = std::min(lo, ib);
-                        hi = std::max(hi, ib);
-                    }
-                }
-                if (hi >= 0) worst = std::max(worst, hi - lo);
-            }
-            return worst;
-        };
-        const int32_t tall_nat = tallest(rows_band);
-        if (tall_nat > 600 && m1 > 1) {
-            std::vector<int32_t> ridx;
-            SX_TRY(down(s, ridx, A->csr_idx, static_cast<size_t>(A->nnz)));
-            SX_HIP(hipStreamSynchronize(s));
-            std::vector<uint8_t> is_band(static_cast<size_t>(m), 0);
-            for (int32_t r : rows_band) is_band[r] = 1;
-            const int64_t col_cap = std::max<int64_t>(64, static_cast<int64_t>(16.0 * static_cast<double>(A->nnz) / static_cast<double>(n)));
-            auto sweep = [&](int32_t start, std::vector<int32_t> &order) { // breadth first over all components, `start` first
-                order.clear();
-                std::vector<uint8_t> seen(static_cast<size_t>(m), 0), used(static_cast<size_t>(n), 0);
-                size_t next_seed = 0;
-                int32_t seed = start;
-                while (static_cast<int64_t>(order.size()) < m1) {
-                    if (seed < 0) {
-                        while (next_seed < rows_band.size() && seen[rows_band[next_seed]]) ++next_seed;
-                        if (next_seed >= rows_band.size()) break;
-                        seed = rows_band[next_seed];
-                    }
-                    size_t head_q = order.size();
-                    seen[seed] = 1;
-                    order.push_back(seed);
-                    for (; head_q < order.size(); ++head_q) {
-                        const int32_t i = order[head_q];
-                        for (int64_t k = rptr[i]; k < rptr[i + 1]; ++k) {
-                            const int32_t j = ridx[k];
-                            if (used[j]) continue;
-                            used[j] = 1;
-                            if (cptr[j + 1] - cptr[j] > col_cap) continue; // a column that touches everything orders nothing
-                            for (int64_t q = cptr[j]; q < cptr[j + 1]; ++q) {
-                                const int32_t i2 = cidx[q];
-                                if (is_band[i2] && !seen[i2]) {
-                                    seen[i2] = 1;
-                                    order.push_back(i2);
-                                }
-                            }
-                        }
-                    }
-                    seed = -1;
-                }
-            };
-            std::vector<int32_t> o1, o2;
-            sweep(rows_band[0], o1);
-            sweep(o1.empty() ? rows_band[0] : o1.back(), o2); // from the far end of the first sweep
-            if (static_cast<int64_t>(o2.size()) == m1) {
-                const int32_t tall_cm = tallest(o2);
-                if (trace) fprintf(stderr, "[sx_crossover_band] tallest column: %d rows in natural order, %d in Cuthill-McKee order\n", tall_nat, tall_cm);
-                if (tall_cm < tall_nat) rows_band = o2;
-            }
-        }
-    }
-    for (int64_t k = 0; k < m1; ++k) {
-        rowb[rows_band[k]] = static_cast<int32_t>(k);
-        eqidx[rows_band[k]] = static_cast<int32_t>(k);
-    }
-    for (int64_t k = 0; k < ndr; ++k) eqidx[rows_dense[k]] = static_cast<int32_t>(m1 + k);
-    int32_t *d_eqidx = nullptr;
-    SX_TRY(dev.get(eqidx.size(), &d_eqidx));
-    SX_TRY(up(s, d_eqidx, eqidx));
-    // ------------------------------------------------------------------ the first basic set
-    const double MARGIN = 1e-7;
-    std::vector<uint8_t> is_basic(static_cast<size_t>(NV), 0); // the variables the next factorisation has to hold
-    std::vector<int32_t> tracked;                               // columns of the tableau that are not basic
-    std::vector<int8_t> atup(static_cast<size_t>(NV), 0);
-    std::vector<double> margin; // of the first guess (empty for a given basis): the border takes its columns in this order
-    // smallest pivot the two LUs accept.  A GUESSED basis (the m largest margins of a first-order point) may hold columns
-    // that are all but dependent -- its basic solution then lies far from the point and phase 1 pays for it pivot by pivot
-    // -- so its LUs set such columns aside (they stay superbasic, a logical takes their place); a basis the simplex has
-    // reached, or one that was given, is kept unless it is singular to working accuracy
-    const double tol_band_guess = getenv("SX_BAND_PIVTOL_B") ? atof(getenv("SX_BAND_PIVTOL_B")) : 1e-3;
-    const double tol_schur_guess = getenv("SX_BAND_PIVTOL_S") ? atof(getenv("SX_BAND_PIVTOL_S")) : 1e-1;
-    const double tol_band_keep = 1e-7, tol_schur_keep = 1e-9;
-    if (vbasis_in) { // a given basis: codes as in output.py (0 basic, -1 at lower, -2 at upper, -3 superbasic at x_start)
-        for (int64_t j = 0; j < n; ++j) {
-            const int code = vb_in[j];
-            if (code == 0) is_basic[j] = 1;
-            else if (code == -3) tracked.push_back(static_cast<int32_t>(j));
-            else {
-                double v = code == -2 ? hu[j] : hl[j];
-                if (std::isinf(v)) v = code == -2 ? hl[j] : hu[j];
-                if (std::isinf(v)) v = 0.0;
-                hx[j] = v;
-            }
-        }
-        for (int64_t i = 0; i < m; ++i)
-            if (cb_in[i] == 0) is_basic[n + i] = 1;
-    } else {
-        SX_TRY(sx_score_rows_dev(ctx, A, x_start, b, nullptr, 0.0, d_tmpm, nullptr)); // slack = b - A x
-        SX_TRY(down(s, hslack, d_tmpm, static_cast<size_t>(m)));
-        SX_HIP(hipStreamSynchronize(s));
-        margin.assign(static_cast<size_t>(NV), -1.0);
-        std::vector<int64_t> cand;
-        for (int64_t j = 0; j < n; ++j) {
-            const double mg = std::min(hx[j] - hl[j], hu[j] - hx[j]);
-            if (std::isinf(hl[j]) && std::isinf(hu[j])) margin[j] = 1e300;
-            else if (mg > MARGIN * (1.0 + std::fabs(hx[j]))) margin[j] = mg;
-            if (margin[j] > 0) cand.push_back(j);
-        }
-        for (int64_t i = 0; i < m; ++i)
-            if (hlt[i] && hslack[i] > MARGIN * (1.0 + std::fabs(hb[i]))) {
-                margin[n + i] = hslack[i];
-                cand.push_back(n + i);
-            }
-        // the m candidates with the largest margins may sit in the basis, the others start superbasic
-        if (static_cast<int64_t>(cand.size()) > m)
-            std::nth_element(cand.begin(), cand.begin() + m, cand.end(),
-                             [&](int64_t a, int64_t bb) { return margin[a] > margin[bb] || (margin[a] == margin[bb] && a < bb); });
-        for (size_t k = 0; k < cand.size(); ++k) {
-            if (static_cast<int64_t>(k) < m) is_basic[cand[k]] = 1;
-            else tracked.push_back(static_cast<int32_t>(cand[k]));
-        }
-        if (trace) fprintf(stderr, "[sx_crossover_band] m=%lld n=%lld: %zu interior candidates, band rows %lld, dense rows %lld\n", (long long)m, (long long)n, cand.size(), (long long)m1, (long long)ndr);
-    }
-    if (trace) fprintf(stderr, "[sx_crossover_band] host copies, row order and first basic set at %.1f ms\n", now() - t_begin);
-    // ------------------------------------------------------------------ the big blocks, allocated beside the matching
-    BigArena arena;
-    {
-        size_t free_b = 0, total_b = 0;
-        SX_HIP(hipMemGetInfo(&free_b, &total_b));
-        // (estimates before the matching: border = dense rows + up to 32 separators of ~128 rows; a twelfth of the border is
-        //  set aside by the dense LU of a guess -- 1,032 of 13,771 at config-5 size, 158 of 2,299 at the headline size)
-        const double mp_est = static_cast<double>(m) + static_cast<double>(ndr) + 33.0 * 400.0 + 2048.0;
-        const double nb_est = static_cast<double>(ndr) + 32.0 * 128.0 + 1024.0;
-        const double track_est = static_cast<double>(tracked.size()) + nb_est / 12.0;
-        const double epoch_est = std::min(std::min(20000.0, std::min(16.0e9, 0.4 * static_cast<double>(free_b)) / (8.0 * mp_est)), 4.0 * (track_est + nb_est / 8.0) + 2048.0);
-        const double want = 8.0 * mp_est * (epoch_est + 2.0 + 1.5 * track_est + 712.0);
-        if (want > 2.0e9 && want < 0.6 * static_cast<double>(free_b) && !getenv("SX_BAND_NO_ARENA")) arena.start(ctx, static_cast<size_t>(want));
-    }
-    // ------------------------------------------------------------------ small per-call blocks
-    TbState *d_st = nullptr;
-    SX_TRY(dev.get(1, &d_st));
-    int32_t *d_pr = nullptr;
-    double *d_gu = nullptr, *d_ebM = nullptr;
-    SX_TRY(dev.get(static_cast<size_t>(TB_K), &d_pr));
-    SX_TRY(dev.get(static_cast<size_t>(TB_K), &d_gu));
-    SX_TRY(dev.get(static_cast<size_t>(TB_EB) * TB_EB, &d_ebM));
-
-    long long tot_iters = 0, tot_pivots = 0, tot_flips = 0, tot_degen = 0;
-    int64_t added_total = 0;
-    int epochs = 0, final_status = 4, bad_epochs = 0, check_epochs = 0;
-    std::vector<double> hy(static_cast<size_t>(m), 0.0);
-    std::vector<int8_t> vstat(static_cast<size_t>(NV), 0); // 0 non-basic at a bound, 1 basic, 2 tracked
-    std::vector<double> xlog(static_cast<size_t>(m), 0.0);  // values of tracked logicals
-    std::vector<int64_t> prev_pos;                          // band position -> the variable that sat there and never moved
-    double viol_max = 0.0, resid_max = 0.0;
-    size_t peak_bytes = 0;
-    bool strict_next = false, strict_tried = false;
-
+    // ---- 2. host copies; 3. plan: rows, the first basic set, the call's blocks
+    HostLp lp;
+    pl::RowPlan rp;
+    pl::BasisState bs;
+    SX_TRY(host_copies(C, l, u, row_is_lt, x_start, vbasis_in, cbasis_in, lp, bs));
+    SX_TRY(plan_rows(C, lp, rp));
+    SX_TRY(first_basic_set(C, lp, rp, x_start, bs));
+    SX_TRY(call_blocks(C, static_cast<int64_t>(rp.rows_dense.size()), bs.tracked.size()));
+    // ---- 4. epochs: factor the basic set, run the simplex on it; three ways of going round again
     for (;;) {
-        ++epochs;
+        ++C.epochs;
         // the basic set is a guess from the margins of the point -- or a given basis whose basic solution turned out far
         // outside the bounds (below): the LUs then set aside what is all but dependent
-        const bool guessed = (epochs == 1 && !vbasis_in) || strict_next;
-        strict_next = false;
-        DevBufs edev; // this epoch's device arrays
-        // ---------------------------------------------------------------- columns to rows: who sits on which band row
-        // Every band row gets at most ONE variable, whose position is the row's: a variable that sat there in the last
-        // factorisation and is still basic stays; a row whose own logical is basic keeps it; the other basic columns are
-        // matched to the free rows greedily by entry size, largest first (large entries on the diagonal, and a band no
-        // wider than a column is tall: a column only ever sits on a row it has an entry in).  A row no column takes holds
-        // a PLACEHOLDER (unit vector; border row "its value = 0"), a column that finds no row goes to the BORDER.
-        std::vector<int64_t> bvar(static_cast<size_t>(m1), -1);
-        std::vector<uint8_t> placed(static_cast<size_t>(NV), 0);
-        if (!prev_pos.empty())
-            for (int64_t p = 0; p < m1; ++p) {
-                const int64_t v = prev_pos[p];
-                if (v >= 0 && is_basic[v] && !placed[v]) {
-                    bvar[p] = v;
-                    placed[v] = 1;
-                }
-            }
-        for (int64_t p = 0; p < m1; ++p) {
-            const int64_t v = n + rows_band[p];
-            if (bvar[p] < 0 && is_basic[v] && !placed[v]) {
-                bvar[p] = v;
-                placed[v] = 1;
-            }
-        }
-        {
-            struct Ent {
-                double a;
-                int32_t ib;
-                int64_t var;
-            };
-            // order: size descending, then variable, then band row -- a stable LSD radix sort on the inverted bits of the
-            // (positive, finite or infinite) size, 16 bits a pass (8e5 candidates in ~10 ms against ~40 for std::sort with the
-            // three-way comparison) -- then every candidate in that order takes its row if both are still free
-            auto place_sorted = [&](std::vector<Ent> &ents) {
-                std::vector<Ent> tmp(ents.size());
-                std::vector<uint32_t> hist(65536);
-                auto key = [](const Ent &e) {
-                    uint64_t bits;
-                    std::memcpy(&bits, &e.a, sizeof(bits));
-                    return ~bits;
-                };
-                for (int pass = 0; pass < 4 && ents.size() > 1; ++pass) {
-                    const int sh = 16 * pass;
-                    std::fill(hist.begin(), hist.end(), 0u);
-                    for (const Ent &e : ents) ++hist[(key(e) >> sh) & 0xFFFF];
-                    uint32_t run = 0;
-                    for (uint32_t &hh_ : hist) {
-                        const uint32_t cc = hh_;
-                        hh_ = run;
-                        run += cc;
-                    }
-                    for (const Ent &e : ents) tmp[hist[(key(e) >> sh) & 0xFFFF]++] = e;
-                    ents.swap(tmp);
-                }
-                for (const Ent &e : ents)
-                    if (!placed[e.var] && bvar[e.ib] < 0) {
-                        bvar[e.ib] = e.var;
-                        placed[e.var] = 1;
-                    }
-            };
-            // Two rounds (the one sort over every entry of every column was 0.16 of the 0.41 s this set-up took at 1e6 rows:
-            // 7e6 candidates of 24 bytes, four passes): first every column's LARGEST entry in a free row competes -- one
-            // candidate per column, and in a column-dominant basis the winner nearly everywhere --, then the columns that lost
-            // theirs compete with all their entries for the rows that are left
-            std::vector<Ent> ents;
-            for (int64_t j = 0; j < n; ++j) {
-                if (!is_basic[j] || placed[j]) continue;
-                Ent best{0.0, -1, j};
-                for (int64_t k = cptr[j]; k < cptr[j + 1]; ++k) {
-                    const int32_t ib = rowb[cidx[k]];
-                    const double a = std::fabs(cval[k]);
-                    if (ib >= 0 && bvar[ib] < 0 && a > 1e-6 && (a > best.a || (a == best.a && ib < best.ib))) best = Ent{a, ib, j};
-                }
-                if (best.ib >= 0) ents.push_back(best);
-            }
-            place_sorted(ents);
-            ents.clear();
-            for (int64_t j = 0; j < n; ++j) {
-                if (!is_basic[j] || placed[j]) continue;
-                const size_t first = ents.size();
-                for (int64_t k = cptr[j]; k < cptr[j + 1]; ++k) {
-                    const int32_t ib = rowb[cidx[k]];
-                    const double a = std::fabs(cval[k]);
-                    if (ib >= 0 && bvar[ib] < 0 && a > 1e-6) ents.push_back(Ent{a, ib, j});
-                }
-                // a column's candidates by band row (a handful: insertion sort), so that the stable sort leaves equal sizes
-                // in (variable, band row) order
-                for (size_t q = first + 1; q < ents.size(); ++q) {
-                    const Ent e = ents[q];
-                    size_t r = q;
-                    for (; r > first && ents[r - 1].ib > e.ib; --r) ents[r] = ents[r - 1];
-                    ents[r] = e;
-                }
-            }
-            place_sorted(ents);
-        }
-        if (trace) fprintf(stderr, "[sx_crossover_band] epoch %d: columns matched to rows at %.1f ms\n", epochs, now() - t_begin);
-        // ---------------------------------------------------------------- blocks: the band cut at SEPARATORS
-        // A panel of the band LU is a chain of 32 dependent column steps on one workgroup (53 us at kl + ku = 230), a band of
-        // 1e5 rows 3,100 of them in a row.  Cut every RL + W positions: W = max(kl, ku) positions (rows AND the columns matched
-        // to them) go to the border as separators -- no column left of a separator reaches a row right of it, or the other way
-        // round -- so the P blocks between them are independent band matrices, factored side by side
-        // (sx_bandlu_factor_blocks_dev; identity padding of kl + ku + 32 positions keeps their memory apart).  The Schur
-        // complement grows by (P - 1) W rows.
-        const int64_t m1_all = m1;
-        int64_t P = 1, RL = m1_all, Wsep = 0, PAD = 0;
-        {
-            int kl0 = 0, ku0 = 0;
-            for (int64_t p = 0; p < m1_all; ++p) {
-                const int64_t v = bvar[p];
-                if (v < 0 || v >= n) continue;
-                for (int64_t k = cptr[v]; k < cptr[v + 1]; ++k) {
-                    const int32_t ib = rowb[cidx[k]];
-                    if (ib >= 0) {
-                        kl0 = std::max<int>(kl0, ib - static_cast<int>(p));
-                        ku0 = std::max<int>(ku0, static_cast<int>(p) - ib);
-                    }
-                }
-            }
-            const int64_t w = std::max(kl0, ku0), pad = ((kl0 + ku0 + 32 + 31) / 32) * 32;
-            int64_t want = getenv("SX_BAND_BLOCKS") ? atoll(getenv("SX_BAND_BLOCKS")) : std::min<int64_t>(32, m1_all / 8192);
-            while (want > 1) { // (2,048 rows of the border are left to placeholders and columns without a row)
-                const int64_t rl = ((m1_all - (want - 1) * w) / want) / 32 * 32;
-                if (w > 0 && rl >= 4 * pad && ndr + (want - 1) * w + 2048 <= MAX_NB) break;
-                --want;
-            }
-            if (want > 1) {
-                P = want;
-                Wsep = w;
-                PAD = pad;
-                RL = ((m1_all - (P - 1) * w) / P) / 32 * 32;
-            }
-        }
-        const int64_t RL_last = m1_all - (P - 1) * (RL + Wsep), stride = RL + PAD;
-        const int64_t m1e = (P - 1) * stride + RL_last, nsep = (P - 1) * Wsep;
-        std::vector<int64_t> bvar_e(static_cast<size_t>(m1e), -2); // (-2: padding, -1: placeholder)
-        std::vector<int32_t> posrow_e(static_cast<size_t>(m1e), -1), old_of_new(static_cast<size_t>(m1e), -1), rows_dense_e(rows_dense);
-        std::vector<int32_t> rowb_e(static_cast<size_t>(m), -1), eqidx_e(static_cast<size_t>(m), 0);
-        rows_dense_e.resize(static_cast<size_t>(ndr + nsep));
-        for (int64_t p = 0; p < m1_all; ++p) {
-            const int64_t b = std::min<int64_t>(p / (RL + Wsep), P - 1), off = p - b * (RL + Wsep);
-            const int32_t row = rows_band[p];
-            if (b < P - 1 && off >= RL) { // a separator: its row joins the dense rows, its column goes to the border
-                rows_dense_e[static_cast<size_t>(ndr + b * Wsep + off - RL)] = row;
-                if (bvar[p] >= 0) placed[bvar[p]] = 0;
-                continue;
-            }
-            const int64_t np = b * stride + off;
-            bvar_e[np] = bvar[p];
-            posrow_e[np] = row;
-            old_of_new[np] = static_cast<int32_t>(p);
-            rowb_e[row] = static_cast<int32_t>(np);
-            eqidx_e[row] = static_cast<int32_t>(np);
-        }
-        for (size_t k = 0; k < rows_dense_e.size(); ++k) eqidx_e[rows_dense_e[k]] = static_cast<int32_t>(m1e + static_cast<int64_t>(k));
-        int32_t *d_eqidx_e = nullptr;
-        SX_TRY(edev.get(eqidx_e.size(), &d_eqidx_e));
-        SX_TRY(up(s, d_eqidx_e, eqidx_e));
-        { // from here on the geometry is this epoch's: band positions with padding, dense rows with the separators' rows
-        const int64_t m1 = m1e, ndr = static_cast<int64_t>(rows_dense_e.size());
-        std::vector<int64_t> &bvar = bvar_e;
-        const std::vector<int32_t> &rows_band = posrow_e, &rows_dense = rows_dense_e, &rowb = rowb_e, &eqidx = eqidx_e;
-        const int32_t *d_eqidx = d_eqidx_e;
-        // band triplets (a placeholder or a logical: the unit vector of the row), band widths
-        std::vector<int32_t> trow, tcol;
-        std::vector<double> tval;
-        trow.reserve(static_cast<size_t>(A->nnz) / 2 + static_cast<size_t>(m1));
-        tcol.reserve(trow.capacity());
-        tval.reserve(trow.capacity());
-        int kl = 0, ku = 0;
-        for (int64_t p = 0; p < m1; ++p) {
-            const int64_t v = bvar[p];
-            if (v < 0 || v >= n) {
-                trow.push_back(static_cast<int32_t>(p));
-                tcol.push_back(static_cast<int32_t>(p));
-                tval.push_back(1.0);
-                continue;
-            }
-            for (int64_t k = cptr[v]; k < cptr[v + 1]; ++k) {
-                const int32_t ib = rowb[cidx[k]];
-                if (ib >= 0) {
-                    trow.push_back(ib);
-                    tcol.push_back(static_cast<int32_t>(p));
-                    tval.push_back(cval[k]);
-                    kl = std::max<int>(kl, ib - static_cast<int>(p));
-                    ku = std::max<int>(ku, static_cast<int>(p) - ib);
-                }
-            }
-        }
-        if (!sx_bandlu_supports(kl, ku)) {
-            sx_set_error("the basis is not a band matrix in the order of the rows (kl = %d, ku = %d after setting %lld dense rows aside)", kl, ku,
-                         (long long)ndr);
-            return SX_ERR_UNSUPPORTED;
-        }
-        if (trace) fprintf(stderr, "[sx_crossover_band] epoch %d: matching and band assembly done at %.1f ms\n", epochs, now() - t_begin);
+        const bool guessed = (C.epochs == 1 && !vbasis_in) || C.strict_next;
+        C.strict_next = false;
+        Epoch E; // this epoch's device arrays and factors
+        pl::match_columns_to_rows(lp.csc(), rp, bs.is_basic, bs.prev_pos, E.mt);
+        if (C.trace) fprintf(stderr, "[sx_crossover_band] epoch %d: columns matched to rows at %.1f ms\n", C.epochs, C.ms());
+        SX_TRY(epoch_geometry(C, lp, rp, E));
         if (probe_only) { // (sx_crossover_band_probe_dev: the matched basis is a band the LU takes -- that was the question)
             result->status = 0;
             return SX_OK;
         }
-        // ---------------------------------------------------------------- factor B11
-        sx_bandlu *lu = nullptr;
-        sx_denselu *dl = nullptr;
-        struct FactorGuard {
-            sx_bandlu *&h;
-            sx_denselu *&d;
-            ~FactorGuard() {
-                if (h) sx_bandlu_destroy(h);
-                if (d) sx_denselu_destroy(d);
-            }
-        } fguard{lu, dl};
-        std::vector<int32_t> ph_row(static_cast<size_t>(m1), -1); // the row whose unit vector a placeholder is
-        int64_t nrep = 0;
-        if (m1 > 0) {
-            int32_t *d_trow = nullptr, *d_tcol = nullptr;
-            double *d_tval = nullptr;
-            DevBufs tdev;
-            SX_TRY(tdev.get(trow.size(), &d_trow));
-            SX_TRY(tdev.get(tcol.size(), &d_tcol));
-            SX_TRY(tdev.get(tval.size(), &d_tval));
-            SX_TRY(up(s, d_trow, trow));
-            SX_TRY(up(s, d_tcol, tcol));
-            SX_TRY(up(s, d_tval, tval));
-            SX_TRY(sx_bandlu_create_dev(ctx, m1, kl, ku, static_cast<int64_t>(tval.size()), d_trow, d_tcol, d_tval, &lu));
-            std::vector<int32_t> rep(static_cast<size_t>(m1)), piv(static_cast<size_t>(m1));
-            SX_TRY(sx_bandlu_factor_blocks_dev(lu, guessed ? tol_band_guess : tol_band_keep, static_cast<int>(P), P > 1 ? stride : m1, P > 1 ? RL : m1, P > 1 ? RL_last : m1, &nrep,
-                                                rep.data(), piv.data()));
-            // a replaced column stands for the unit vector of the row that sat on its diagonal: a placeholder; the column
-            // itself goes to the border
-            std::vector<int32_t> rowof(static_cast<size_t>(m1));
-            std::iota(rowof.begin(), rowof.end(), 0);
-            for (int64_t j = 0; j < m1; ++j) {
-                if (rep[j]) {
-                    if (bvar[j] >= 0) placed[bvar[j]] = 0;
-                    bvar[j] = -1;
-                    ph_row[j] = rows_band[rowof[j]];
-                } else {
-                    if (piv[j] != j) std::swap(rowof[j], rowof[piv[j]]);
-                    if (bvar[j] == -1) ph_row[j] = rows_band[j];
-                }
-            }
-        }
-        if (trace) fprintf(stderr, "[sx_crossover_band] epoch %d: band LU done at %.1f ms (kl=%d ku=%d, %lld blocks of %lld positions with separators of %lld, %lld columns set aside)\n", epochs, now() - t_begin, kl, ku, (long long)P, (long long)RL, (long long)Wsep, (long long)nrep);
-        // ---------------------------------------------------------------- the border: as many columns as rows
-        auto untrack = [&](int64_t v) { tracked.erase(std::remove(tracked.begin(), tracked.end(), static_cast<int32_t>(v)), tracked.end()); };
-        std::vector<int64_t> bcol;
-        for (int64_t v = 0; v < NV; ++v)
-            if (is_basic[v] && !placed[v]) bcol.push_back(v);
-        int64_t h = 0;
-        for (int64_t p = 0; p < m1; ++p) h += bvar[p] == -1;
-        {
-            // too few columns for the border rows (or a border beyond the dense LU): placeholders become their row's own
-            // logical, then the dense rows' logicals fill in; too many: the surplus leaves the basis (superbasic)
-            std::vector<int32_t> gone;
-            for (int64_t p = 0; p < m1 && (static_cast<int64_t>(bcol.size()) < ndr + h || ndr + h > MAX_NB); ++p) {
-                if (bvar[p] != -1) continue;
-                const int64_t w = n + ph_row[p];
-                if (is_basic[w]) continue;
-                bvar[p] = w;
-                is_basic[w] = 1;
-                placed[w] = 1;
-                gone.push_back(static_cast<int32_t>(w));
-                --h;
-            }
-            for (int64_t k = 0; k < ndr && static_cast<int64_t>(bcol.size()) < ndr + h; ++k) {
-                const int64_t w = n + rows_dense[k];
-                if (is_basic[w]) continue;
-                is_basic[w] = 1;
-                bcol.push_back(w);
-                gone.push_back(static_cast<int32_t>(w));
-            }
-            if (!gone.empty()) {
-                std::vector<uint8_t> g(static_cast<size_t>(NV), 0);
-                for (int32_t w : gone) g[w] = 1;
-                tracked.erase(std::remove_if(tracked.begin(), tracked.end(), [&](int32_t v) { return g[v] != 0; }), tracked.end());
-            }
-            if (guessed && !margin.empty()) // the surest columns first: a column the dense LU sets aside is one of the doubtful ones
-                std::sort(bcol.begin(), bcol.end(), [&](int64_t a, int64_t bb) { return margin[a] > margin[bb] || (margin[a] == margin[bb] && a < bb); });
-            else std::sort(bcol.begin(), bcol.end());
-            while (static_cast<int64_t>(bcol.size()) > ndr + h) {
-                const int64_t v = bcol.back();
-                bcol.pop_back();
-                is_basic[v] = 0;
-                tracked.push_back(static_cast<int32_t>(v));
-            }
-            if (static_cast<int64_t>(bcol.size()) != ndr + h || ndr + h > MAX_NB) {
-                sx_set_error("the border of the basis has %lld rows and %zu columns (at most %lld rows)", (long long)(ndr + h), bcol.size(), (long long)MAX_NB);
-                return SX_ERR_UNSUPPORTED;
-            }
-        }
-        const int64_t nb = ndr + h, mp = m1 + nb;
-        // the eta file of this epoch -- allocated now because its memory doubles as the work block of the Schur complement's
-        // assembly (a block of 24 GB allocated and freed for that alone cost 0.3 s at 1e5 rows and 1.2 s at 1e6: hipFree of a
-        // touched block).  Basis changes before the basis is factored afresh: a few times the columns that can move, within
-        // 16 GB; a fresh factorisation keeps every basic variable (bordered form), so the file need not be long
-        double *d_eta = nullptr;
-        int32_t *d_eta_r = nullptr;
-        int64_t EPOCH = 0;
-        {
-            size_t free_b = 0, total_b = 0;
-            SX_HIP(hipMemGetInfo(&free_b, &total_b));
-            const int64_t by_memory = std::max<int64_t>(64, static_cast<int64_t>(std::min(16.0e9, 0.4 * static_cast<double>(free_b)) / (8.0 * static_cast<double>(mp))) - 1);
-            EPOCH = std::min<int64_t>(std::min<int64_t>(20000, by_memory), 4 * static_cast<int64_t>(tracked.size() + static_cast<size_t>(nb) / 8) + 2048);
-            if (const char *e = getenv("SX_BAND_EPOCH")) EPOCH = std::max<int64_t>(16, atoll(e));
-            arena.reset(); // (what the last epoch held there is dead)
-            d_eta = static_cast<double *>(arena.take(sizeof(double) * static_cast<size_t>(mp) * (EPOCH + 1)));
-            if (!d_eta) SX_TRY(edev.get(static_cast<size_t>(mp) * (EPOCH + 1), &d_eta));
-            SX_TRY(edev.get(static_cast<size_t>(EPOCH) + 2, &d_eta_r));
-        }
-        std::vector<int32_t> ph_pos;
-        for (int64_t p = 0; p < m1; ++p)
-            if (bvar[p] == -1) ph_pos.push_back(static_cast<int32_t>(p));
-        // ---- B21: the dense rows' entries in the band columns, one unit entry per placeholder row
-        SxBorderOps ops;
-        ops.ctx = ctx;
-        ops.m1 = m1;
-        ops.nb = nb;
-        ops.mp = mp;
-        ops.lu = lu;
-        ops.tiny = TB_TINY;
-        auto rows_to_dev = [&](const HostRows &R, int64_t nrows, bool with_list, SxRowsDev &out) -> int {
-            int64_t *dp = nullptr;
-            int32_t *di = nullptr, *dlist = nullptr;
-            double *dv = nullptr;
-            SX_TRY(edev.get(R.ptr.size(), &dp));
-            SX_TRY(edev.get(R.idx.size(), &di));
-            SX_TRY(edev.get(R.val.size(), &dv));
-            SX_TRY(up(s, dp, R.ptr));
-            SX_TRY(up(s, di, R.idx));
-            SX_TRY(up(s, dv, R.val));
-            if (with_list) {
-                SX_TRY(edev.get(R.list.size(), &dlist));
-                SX_TRY(up(s, dlist, R.list));
-            }
-            out.nrows = nrows;
-            out.ptr = dp;
-            out.idx = di;
-            out.val = dv;
-            out.list = dlist;
-            return SX_OK;
-        };
-        HostRows b21r, b21c, b12r, b12c;
-        if (nb > 0) {
-            std::vector<int32_t> er, ep;
-            std::vector<double> ev;
-            for (int64_t p = 0; p < m1; ++p) {
-                const int64_t v = bvar[p];
-                if (v < 0 || v >= n) continue;
-                for (int64_t k = cptr[v]; k < cptr[v + 1]; ++k)
-                    if (rowb[cidx[k]] < 0) {
-                        er.push_back(eqidx[cidx[k]] - static_cast<int32_t>(m1));
-                        ep.push_back(static_cast<int32_t>(p));
-                        ev.push_back(cval[k]);
-                    }
-            }
-            for (size_t t = 0; t < ph_pos.size(); ++t) {
-                er.push_back(static_cast<int32_t>(ndr + static_cast<int64_t>(t)));
-                ep.push_back(ph_pos[t]);
-                ev.push_back(1.0);
-            }
-            rows_from_triplets(nb, er, ep, ev, false, b21r);
-            rows_from_triplets(m1, ep, er, ev, true, b21c);
-            SX_TRY(rows_to_dev(b21r, nb, false, ops.b21_rows));
-            SX_TRY(rows_to_dev(b21c, static_cast<int64_t>(b21c.list.size()), true, ops.b21_cols));
-        }
-        // ---- the Schur complement, a block of border columns at a time: S[:, j] = (a2 - B21 B11^-1 a1) of column j
-        int64_t nrep2 = 0;
-        if (nb > 0) {
-            {
-                size_t free_b = 0, total_b = 0;
-                SX_HIP(hipMemGetInfo(&free_b, &total_b));
-                ops.v_limit = static_cast<size_t>(std::min(4.0e9, 0.05 * static_cast<double>(free_b)) / 8.0);
-                if (getenv("SX_BAND_NO_V")) ops.v_failed = 1;
-            }
-            SX_TRY(sx_denselu_create_dev(ctx, nb, &dl));
-            double *Sa = nullptr;
-            int64_t Sld = 0;
-            SX_TRY(sx_denselu_matrix(dl, &Sa, &Sld));
-            // blocks of up to 4,096 columns (in the memory of the still empty eta file: a sparse band solve is a chain of panel steps per
-            // group of 8 columns whatever the number of groups, 250 columns a launch kept 31 of 256 CUs busy), taken in the
-            // order of the VARIABLES -- neighbours in that order live in neighbouring rows, so the 8 columns of a group share
-            // their panels -- and written to the column of S the border's own order gives them
-            const int64_t CH = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nb, 4096), EPOCH + 1));
-            DevBufs sdev;
-            double *Wc = d_eta; // (the eta file is empty until the simplex starts)
-            int32_t *d_bvars = nullptr, *d_dest = nullptr;
-            SX_TRY(sdev.get(static_cast<size_t>(nb), &d_bvars));
-            SX_TRY(sdev.get(static_cast<size_t>(nb), &d_dest));
-            std::vector<int32_t> order(static_cast<size_t>(nb)), bv32(static_cast<size_t>(nb));
-            std::iota(order.begin(), order.end(), 0);
-            std::sort(order.begin(), order.end(), [&](int32_t a, int32_t bb) { return bcol[a] < bcol[bb]; });
-            for (int64_t t = 0; t < nb; ++t) bv32[t] = static_cast<int32_t>(bcol[order[t]]);
-            SX_TRY(up(s, d_bvars, bv32));
-            SX_TRY(up(s, d_dest, order));
-            peak_bytes = std::max(peak_bytes, sizeof(double) * (static_cast<size_t>(mp) * (EPOCH + 1) + static_cast<size_t>(Sld) * nb));
-            for (int64_t c0 = 0; c0 < nb; c0 += CH) {
-                const int64_t kc = std::min<int64_t>(CH, nb - c0);
-                SX_HIP(hipMemsetAsync(Wc, 0, sizeof(double) * static_cast<size_t>(mp) * kc, s));
-                hipLaunchKernelGGL(k_tb_scatter_cols, dim3(gridof(kc)), dim3(TB_WG), 0, s, kc, d_bvars + c0, n, A->csc_ptr, A->csc_idx, A->csc_val, d_eqidx, Wc, mp);
-                SX_TRY(ops.ftran(Wc, kc, true, true));
-                SX_TRY(ops.pack_v(Wc, kc, order.data() + c0)); // (the band parts B11^-1 B12 of these columns, by their windows)
-                hipLaunchKernelGGL(k_tb_copy_cols, dim3(static_cast<unsigned>(std::min<int64_t>(gridof(nb), 64)), static_cast<unsigned>(kc)), dim3(TB_WG), 0, s, nb, Wc + m1, mp,
-                                   d_dest + c0, Sa, Sld);
-            }
-            SX_HIP(hipStreamSynchronize(s));
-            if (trace) fprintf(stderr, "[sx_crossover_band] epoch %d: Schur complement (%lld rows: %lld dense, %lld placeholders) assembled at %.1f ms\n", epochs, (long long)nb, (long long)ndr, (long long)h, now() - t_begin);
-            std::vector<int32_t> rep2(static_cast<size_t>(nb)), perm2(static_cast<size_t>(nb));
-            SX_TRY(sx_denselu_factor_dev(dl, guessed ? tol_schur_guess : tol_schur_keep, &nrep2, rep2.data(), perm2.data()));
-            // a border column without a pivot leaves the basis (it stays in the tableau); what takes its place is the unit
-            // vector of the border row on its diagonal: a dense row's logical -- or, for a placeholder's row, the
-            // placeholder turns into its row's real logical (and the border column into its mirror image, a dummy)
-            // (all of them leave first: the logical a replaced column stands for may itself be a later border column that
-            //  the same elimination set aside)
-            for (int64_t j = 0; j < nb; ++j)
-                if (rep2[j]) {
-                    is_basic[bcol[j]] = 0;
-                    tracked.push_back(static_cast<int32_t>(bcol[j]));
-                }
-            for (int64_t j = 0; j < nb; ++j) {
-                if (!rep2[j]) continue;
-                const int64_t r = perm2[j];
-                int64_t w;
-                if (r < ndr) {
-                    w = n + rows_dense[r];
-                    bcol[j] = w;
-                } else {
-                    const int64_t p = ph_pos[static_cast<size_t>(r - ndr)];
-                    w = n + ph_row[p];
-                    bvar[p] = w;
-                    bcol[j] = -1;
-                }
-                if (is_basic[w]) {
-                    sx_set_error("internal: the repair of the Schur complement wants logical %lld twice", (long long)(w - n));
-                    return SX_ERR_UNSUPPORTED;
-                }
-                is_basic[w] = 1;
-                untrack(w);
-            }
-            SX_TRY(ops.finish_v(rep2)); // (a column that left the basis: its V column is zero, like the unit vector's that replaced it)
-            if (trace) {
-                std::vector<double> dg(static_cast<size_t>(nb));
-                SX_HIP(hipMemcpy2D(dg.data(), sizeof(double), Sa, sizeof(double) * (Sld + 1), sizeof(double), static_cast<size_t>(nb), hipMemcpyDeviceToHost));
-                double mn = INFINITY;
-                int64_t c2 = 0, c4 = 0, c6 = 0;
-                for (double d : dg) {
-                    const double a = std::fabs(d);
-                    mn = std::min(mn, a);
-                    c2 += a < 1e-2;
-                    c4 += a < 1e-4;
-                    c6 += a < 1e-6;
-                }
-                fprintf(stderr, "[sx_crossover_band] epoch %d: Schur complement factored at %.1f ms (%lld columns set aside; smallest pivot %.2e, %lld / %lld / %lld below 1e-2 / 1e-4 / 1e-6); "
-                                "B11^-1 B12 %s: %.1f rows per border column, %.3f GB\n",
-                        epochs, now() - t_begin, (long long)nrep2, mn, (long long)c2, (long long)c4, (long long)c6, ops.v_ready ? "packed by windows" : "not kept (solve form)",
-                        static_cast<double>(ops.v_used) / static_cast<double>(nb), static_cast<double>(ops.v_used) * 8e-9);
-            }
-        }
-        ops.dl = dl;
-        // ---- B12: the border columns' entries in the band rows
-        if (nb > 0 && m1 > 0) {
-            std::vector<int32_t> ep, ej;
-            std::vector<double> ev;
-            for (int64_t j = 0; j < nb; ++j) {
-                const int64_t v = bcol[j];
-                if (v < 0) continue;
-                if (v >= n) {
-                    if (rowb[v - n] >= 0) {
-                        ep.push_back(rowb[v - n]);
-                        ej.push_back(static_cast<int32_t>(j));
-                        ev.push_back(1.0);
-                    }
-                    continue;
-                }
-                for (int64_t k = cptr[v]; k < cptr[v + 1]; ++k)
-                    if (rowb[cidx[k]] >= 0) {
-                        ep.push_back(rowb[cidx[k]]);
-                        ej.push_back(static_cast<int32_t>(j));
-                        ev.push_back(cval[k]);
-                    }
-            }
-            rows_from_triplets(m1, ep, ej, ev, true, b12r);
-            rows_from_triplets(nb, ej, ep, ev, false, b12c);
-            SX_TRY(rows_to_dev(b12r, static_cast<int64_t>(b12r.list.size()), true, ops.b12_rows));
-            SX_TRY(rows_to_dev(b12c, nb, false, ops.b12_cols));
-            ops.work_cols = ops.v_ready ? 1 : std::max<int64_t>(1, std::min<int64_t>(128, static_cast<int64_t>(1.0e9 / (8.0 * static_cast<double>(m1)))));
-            SX_TRY(edev.get(static_cast<size_t>(m1) * ops.work_cols, &ops.work));
-        }
-        if (trace) {
-            SX_HIP(hipStreamSynchronize(s));
-            fprintf(stderr, "[sx_crossover_band] epoch %d: border blocks in place at %.1f ms\n", epochs, now() - t_begin);
-        }
-        // ---- who is where
-        std::vector<int64_t> head(static_cast<size_t>(mp), -1);
-        for (int64_t p = 0; p < m1; ++p) head[p] = bvar[p];
-        for (int64_t j = 0; j < nb; ++j) head[m1 + j] = bcol[j];
-        std::fill(vstat.begin(), vstat.end(), 0);
-        int64_t n_basic = 0, n_dummy = 0;
-        for (int64_t p = 0; p < mp; ++p) {
-            if (head[p] < 0) {
-                ++n_dummy;
-                continue;
-            }
-            if (vstat[head[p]] == 1) {
-                sx_set_error("internal: variable %lld covers two positions of the basis", (long long)head[p]);
-                return SX_ERR_UNSUPPORTED;
-            }
-            vstat[head[p]] = 1;
-            ++n_basic;
-        }
-        if (n_basic != m) {
-            sx_set_error("internal: %lld basic variables for %lld rows", (long long)n_basic, (long long)m);
-            return SX_ERR_UNSUPPORTED;
-        }
-        for (int64_t v = 0; v < NV; ++v) is_basic[v] = vstat[v] == 1;
-        std::vector<int32_t> varJ;
-        for (int32_t v : tracked)
-            if (vstat[v] == 0) {
-                vstat[v] = 2;
-                varJ.push_back(v);
-            }
-        std::sort(varJ.begin(), varJ.end()); // (neighbours in the order of the variables share the panels of a sparse band solve)
-        int64_t nJ = static_cast<int64_t>(varJ.size());
-        // ---------------------------------------------------------------- this epoch's blocks: positions, tableau, eta file
-        const int nblk = static_cast<int>(gridof(mp));
-        double *d_xB = nullptr, *d_lB = nullptr, *d_uB = nullptr, *d_cB = nullptr, *d_g = nullptr, *d_vec = nullptr, *d_part = nullptr, *d_infpart = nullptr, *d_etp = nullptr;
-        int32_t *d_head = nullptr, *d_blist = nullptr, *d_infoff = nullptr, *d_inflist = nullptr;
-        TbPart *d_rpart = nullptr;
-        SX_TRY(edev.get(static_cast<size_t>(mp), &d_xB));
-        SX_TRY(edev.get(static_cast<size_t>(mp), &d_lB));
-        SX_TRY(edev.get(static_cast<size_t>(mp), &d_uB));
-        SX_TRY(edev.get(static_cast<size_t>(mp), &d_cB));
-        SX_TRY(edev.get(static_cast<size_t>(mp), &d_g));
-        SX_TRY(edev.get(static_cast<size_t>(mp), &d_vec));
-        SX_TRY(edev.get(static_cast<size_t>(mp), &d_head));
-        SX_TRY(edev.get(static_cast<size_t>(2 * nblk), &d_part));
-        SX_TRY(edev.get(static_cast<size_t>(TB_EB) * TB_ETS, &d_etp));
-        SX_TRY(edev.get(static_cast<size_t>(nblk), &d_blist));
-        SX_TRY(edev.get(static_cast<size_t>(2 * nblk), &d_infpart));
-        SX_TRY(edev.get(static_cast<size_t>(nblk), &d_infoff));
-        SX_TRY(edev.get(static_cast<size_t>(TB_INFLIST), &d_inflist));
-        SX_TRY(edev.get(static_cast<size_t>(nblk), &d_rpart));
-        TbSlots sl;
-        {
-            size_t free_b = 0, total_b = 0;
-            SX_HIP(hipMemGetInfo(&free_b, &total_b));
-            int64_t cap0 = nJ + std::max<int64_t>(512, nJ / 2); // (growing it later is an allocation, a copy and a free of GBs)
-            if (static_cast<double>(TbSlots::bytes_for(mp, cap0)) > 0.6 * static_cast<double>(free_b)) cap0 = nJ + 16;
-            if (static_cast<double>(TbSlots::bytes_for(mp, cap0)) > 0.8 * static_cast<double>(free_b)) {
-                sx_set_error("the tableau of %lld tracked columns over %lld positions does not fit the free device memory", (long long)cap0, (long long)mp);
-                return SX_ERR_NOMEM;
-            }
-            SX_TRY(sl.reserve(s, mp, cap0, 0, &arena));
-            peak_bytes = std::max(peak_bytes, TbSlots::bytes_for(mp, cap0) + sizeof(double) * static_cast<size_t>(mp) * (EPOCH + 1));
-        }
-        if (trace) fprintf(stderr, "[sx_crossover_band] epoch %d: tableau and position blocks allocated at %.1f ms\n", epochs, now() - t_begin);
-        // ---------------------------------------------------------------- values: non-basic and tracked columns, right-hand side
-        // logical of row i: s_i = b_i - (A x)_i for the tracked ones (their current value), 0 for the non-basic ones
-        SX_TRY(up(s, d_tmpn, hx));
-        SX_TRY(sx_score_rows_dev(ctx, A, d_tmpn, b, nullptr, 0.0, d_tmpm, nullptr));
-        SX_TRY(down(s, hslack, d_tmpm, static_cast<size_t>(m)));
-        SX_HIP(hipStreamSynchronize(s));
-        std::vector<double> xN(hx);
-        for (int64_t j = 0; j < n; ++j) {
-            if (vstat[j] == 1) xN[j] = 0.0;
-            else if (vstat[j] == 0) {
-                const bool upb = (hu[j] - hx[j]) < (hx[j] - hl[j]);
-                double v = upb ? hu[j] : hl[j];
-                if (std::isinf(v)) v = 0.0;
-                xN[j] = v;
-                hx[j] = v;
-                atup[j] = upb;
-            }
-        }
-        for (int64_t i = 0; i < m; ++i) {
-            xlog[i] = 0.0;
-            if (vstat[n + i] == 2) xlog[i] = hlt[i] ? std::max(hslack[i], 0.0) : 0.0;
-        }
-        SX_TRY(up(s, d_tmpn, xN));
-        SX_TRY(sx_score_rows_dev(ctx, A, d_tmpn, b, nullptr, 0.0, d_tmpm, nullptr));
-        std::vector<double> hr;
-        SX_TRY(down(s, hr, d_tmpm, static_cast<size_t>(m)));
-        SX_HIP(hipStreamSynchronize(s));
-        std::vector<double> rp(static_cast<size_t>(mp), 0.0); // (a placeholder's border row: 0)
-        for (int64_t i = 0; i < m; ++i) rp[eqidx[i]] = hr[i] - xlog[i];
-        // solve helper: row-space columns through the bordered factors, then the eta file
-        auto ftran_cols = [&](double *W, int64_t ncols, int64_t n_eta_now, bool lp_columns) -> int {
-            if (ncols == 0) return SX_OK;
-            SX_TRY(ops.ftran(W, ncols, lp_columns));
-            if (n_eta_now > 0) { // (what the tableau would drop anyway goes first: the list of an eta holds real entries only)
-                hipLaunchKernelGGL(k_tb_drop, dim3(gridcap(mp * ncols)), dim3(TB_WG), 0, s, mp * ncols, W, TB_DROP);
-            }
-            for (int64_t k0 = 0; k0 < n_eta_now; k0 += TB_EB) {
-                const int K = static_cast<int>(std::min<int64_t>(TB_EB, n_eta_now - k0));
-                hipLaunchKernelGGL(k_tb_etab_gather, dim3(gridof(std::max<int64_t>(TB_EB * ncols, TB_EB * TB_EB))), dim3(TB_WG), 0, s, mp, ncols, W, d_eta,
-                                   d_eta_r, k0, K, sl.ebG, d_ebM);
-                hipLaunchKernelGGL(k_tb_etab_solve, dim3(static_cast<unsigned>((ncols + 63) / 64)), dim3(64), 0, s, ncols, sl.ebG, d_ebM, sl.ebS, sl.elist);
-                hipLaunchKernelGGL(k_tb_etab_apply, dim3(static_cast<unsigned>(std::min(nblk, 1024)), static_cast<unsigned>((ncols + TB_EC - 1) / TB_EC)),
-                                   dim3(TB_WG), 0, s, mp, ncols, W, d_eta, d_eta_r, k0, K, sl.ebS, sl.elist);
-            }
-            SX_HIP(hipGetLastError());
-            return SX_OK;
-        };
-        // ---- basic variables (a dummy -- placeholder or mirror column -- is free, costs nothing and never leaves)
-        {
-            std::vector<double> hlB(static_cast<size_t>(mp)), huB(static_cast<size_t>(mp)), hcB(static_cast<size_t>(mp));
-            std::vector<int32_t> hhead(static_cast<size_t>(mp));
-            for (int64_t p = 0; p < mp; ++p) {
-                hhead[p] = static_cast<int32_t>(head[p]);
-                if (head[p] < 0) {
-                    hlB[p] = -INFINITY;
-                    huB[p] = INFINITY;
-                    hcB[p] = 0.0;
-                    continue;
-                }
-                hlB[p] = var_lo(head[p]);
-                huB[p] = var_up(head[p]);
-                hcB[p] = var_cost(head[p]);
-            }
-            SX_TRY(up(s, d_head, hhead));
-            SX_TRY(up(s, d_lB, hlB));
-            SX_TRY(up(s, d_uB, huB));
-            SX_TRY(up(s, d_cB, hcB));
-            SX_TRY(up(s, d_xB, rp));
-            SX_HIP(hipStreamSynchronize(s));
-        }
-        if (trace) fprintf(stderr, "[sx_crossover_band] epoch %d: right-hand side and basic variables' arrays at %.1f ms\n", epochs, now() - t_begin);
-        SX_TRY(ftran_cols(d_xB, 1, 0, false));
-        if (vbasis_in && epochs == 1 && !strict_tried) {
-            // a GIVEN basis is kept as it is (tolerances of a basis the simplex has reached) -- unless its basic solution says it
-            // is no basis to start from: members that are all but dependent put it far outside the bounds, and phase 1 would
-            // pay for each of them pivot by pivot (15 wrong members of 1,200: 6,537 iterations against 402 from the point alone).
-            // Then the same set is factored once more with the tolerances of a guess
-            std::vector<double> t;
-            SX_TRY(down(s, t, d_xB, static_cast<size_t>(mp)));
-            SX_HIP(hipStreamSynchronize(s));
-            double worst = 0.0;
-            int64_t ninf = 0;
-            for (int64_t p = 0; p < mp; ++p) {
-                if (head[p] < 0) continue;
-                const double vi = std::max(var_lo(head[p]) - t[p], t[p] - var_up(head[p]));
-                if (vi > feas_tol) ++ninf;
-                worst = std::max(worst, vi);
-            }
-            strict_tried = true;
-            if (worst > 1.0 || ninf > std::max<int64_t>(16, m / 50)) {
-                if (trace) fprintf(stderr, "[sx_crossover_band] the given basis puts %lld variables outside their bounds (worst %.3e): factored again with the tolerances of a guess\n", (long long)ninf, worst);
-                strict_next = true;
+        SX_TRY(factor_band(C, E, guessed));
+        SX_TRY(make_border(C, lp, bs, E, guessed));
+        SX_TRY(schur_complement(C, bs, E, guessed));
+        SX_TRY(border_blocks(C, lp, E));
+        SX_TRY(epoch_arrays(C, bs, E));
+        SX_TRY(values_and_rhs(C, lp, bs, E));
+        if (vbasis_in && C.epochs == 1 && !C.strict_tried) { // (1) a given basis that is no basis to start from
+            bool far = false;
+            SX_TRY(given_basis_is_far(C, lp, E, far));
+            C.strict_tried = true;
+            if (far) {
+                C.strict_next = true;
                 continue;
             }
         }
-        if (trace) { // how far the basic solution is from the point handed over (conditioning of the guessed basis)
-            std::vector<double> t;
-            SX_TRY(down(s, t, d_xB, static_cast<size_t>(mp)));
-            SX_HIP(hipStreamSynchronize(s));
-            double devi = 0.0, worst = 0.0, dummy = 0.0;
-            int64_t ninf = 0, inf_bs = 0, inf_bl = 0, inf_border = 0, border_struct = 0;
-            for (int64_t j = 0; j < nb; ++j) border_struct += bcol[j] >= 0 && bcol[j] < n;
-            for (int64_t p = 0; p < mp; ++p) {
-                const int64_t v = head[p];
-                if (v < 0) {
-                    if (p < m1) dummy = std::max(dummy, std::fabs(t[p]));
-                    continue;
-                }
-                const double ref = v < n ? hx[v] : (hlt[v - n] ? std::max(hslack[v - n], 0.0) : 0.0);
-                devi = std::max(devi, std::fabs(t[p] - ref));
-                const double vi = std::max(var_lo(v) - t[p], t[p] - var_up(v));
-                if (vi > feas_tol) {
-                    ++ninf;
-                    if (p >= m1) ++inf_border;
-                    else if (v < n) ++inf_bs;
-                    else ++inf_bl;
-                }
-                worst = std::max(worst, vi);
-            }
-            fprintf(stderr, "[sx_crossover_band] epoch %d: outside their bounds: %lld band columns, %lld band logicals, %lld border variables (the border holds %lld columns, %lld logicals)\n",
-                    epochs, (long long)inf_bs, (long long)inf_bl, (long long)inf_border, (long long)border_struct, (long long)(nb - border_struct));
-            fprintf(stderr, "[sx_crossover_band] epoch %d: basic solution deviates from the point by at most %.3e; %lld basic variables outside their bounds (worst %.3e); "
-                            "placeholders hold at most %.1e; %.1f ms\n", epochs, devi, (long long)ninf, worst, dummy, now() - t_begin);
-        }
-        // ---- tracked columns
-        auto value_of = [&](int64_t v) { return v < n ? hx[v] : xlog[v - n]; };
-        auto load_slots = [&](int64_t s0, const std::vector<int32_t> &vars) -> int {
-            const size_t k = vars.size();
-            if (k == 0) return SX_OK;
-            std::vector<double> vx(k), vl(k), vu(k), vc(k);
-            std::vector<int32_t> vs(k);
-            for (size_t t = 0; t < k; ++t) {
-                const int64_t v = vars[t];
-                vl[t] = var_lo(v);
-                vu[t] = var_up(v);
-                vc[t] = var_cost(v);
-                vx[t] = std::min(std::max(value_of(v), vl[t]), vu[t]);
-                if (vx[t] > vl[t] && vx[t] < vu[t]) vs[t] = TB_SUP;
-                else vs[t] = (vx[t] >= vu[t] && vu[t] > vl[t]) ? TB_UPP : TB_LOW;
-            }
-            SX_HIP(hipMemcpyAsync(sl.varJ + s0, vars.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, s));
-            SX_HIP(hipMemcpyAsync(sl.xJ + s0, vx.data(), sizeof(double) * k, hipMemcpyHostToDevice, s));
-            SX_HIP(hipMemcpyAsync(sl.lJ + s0, vl.data(), sizeof(double) * k, hipMemcpyHostToDevice, s));
-            SX_HIP(hipMemcpyAsync(sl.uJ + s0, vu.data(), sizeof(double) * k, hipMemcpyHostToDevice, s));
-            SX_HIP(hipMemcpyAsync(sl.cJ + s0, vc.data(), sizeof(double) * k, hipMemcpyHostToDevice, s));
-            SX_HIP(hipMemcpyAsync(sl.statJ + s0, vs.data(), sizeof(int32_t) * k, hipMemcpyHostToDevice, s));
-            SX_HIP(hipStreamSynchronize(s)); // (the staging vectors go out of scope)
-            return SX_OK;
-        };
-        auto build_cols = [&](int64_t s0, int64_t k, int64_t n_eta_now) -> int {
-            if (k == 0) return SX_OK;
-            double *W = sl.T + static_cast<size_t>(s0) * mp;
-            SX_HIP(hipMemsetAsync(W, 0, sizeof(double) * static_cast<size_t>(mp) * k, s));
-            hipLaunchKernelGGL(k_tb_scatter_cols, dim3(gridof(k)), dim3(TB_WG), 0, s, k, sl.varJ + s0, n, A->csc_ptr, A->csc_idx, A->csc_val, d_eqidx, W, mp);
-            SX_TRY(ftran_cols(W, k, n_eta_now, true));
-            hipLaunchKernelGGL(k_tb_drop, dim3(gridcap(mp * k)), dim3(TB_WG), 0, s, mp * k, W, 10.0 * TB_DROP);
-            // reduced costs of the new columns under the current basis: d = c_J - c_B^T T
-            hipLaunchKernelGGL(k_tb_coldot, dim3(static_cast<unsigned>(k)), dim3(TB_WG), 0, s, mp, W, d_cB, sl.cJ + s0, sl.dJ + s0);
-            SX_HIP(hipGetLastError());
-            return SX_OK;
-        };
-        SX_TRY(load_slots(0, varJ));
-        SX_TRY(build_cols(0, nJ, 0));
-        if (trace) {
-            SX_HIP(hipStreamSynchronize(s));
-            fprintf(stderr, "[sx_crossover_band] epoch %d: tableau columns (FTRAN of %lld) done at %.1f ms\n", epochs, (long long)nJ, now() - t_begin);
-        }
-        TbState hst{};
-        hst.max_iter = max_iter - tot_iters;
-        hst.cap_eta = EPOCH;
-        hst.feas_tol = feas_tol;
-        hst.opt_tol = opt_tol;
-        SX_HIP(hipMemcpyAsync(d_st, &hst, sizeof(hst), hipMemcpyHostToDevice, s));
-        SX_HIP(hipStreamSynchronize(s));
-        if (trace)
-            fprintf(stderr, "[sx_crossover_band] epoch %d: %lld positions (%lld band + %lld border, %lld dummies), %lld tracked columns (tableau capacity %lld = %.2f GB, "
-                            "eta file %lld = %.2f GB); %.1f ms so far\n", epochs, (long long)mp, (long long)m1, (long long)nb, (long long)n_dummy, (long long)nJ,
-                    (long long)sl.cap, static_cast<double>(mp) * sl.cap * 8e-9, (long long)EPOCH, static_cast<double>(mp) * (EPOCH + 1) * 8e-9, now() - t_begin);
-        // ---------------------------------------------------------------- the simplex on the tracked columns
-        auto one_pivot = [&]() {
-            const TbPend pend{sl.vbuf, d_pr, sl.s0, sl.sbase, sl.cap};
-            hipLaunchKernelGGL(k_tb_infeas, dim3(nblk), dim3(TB_WG), 0, s, mp, d_xB, d_lB, d_uB, d_st, d_g, d_infpart);
-            hipLaunchKernelGGL(k_tb_phase, dim3(1), dim3(TB_WG), 0, s, nblk, d_infpart, d_st, d_infoff);
-            hipLaunchKernelGGL(k_tb_inflist, dim3(nblk), dim3(TB_WG), 0, s, mp, d_g, d_infpart, d_infoff, d_st, d_inflist);
-            hipLaunchKernelGGL(k_tb_gu, dim3(TB_K), dim3(TB_WG), 0, s, mp, nblk, d_eta, d_g, d_inflist, d_st, pend, d_gu);
-            hipLaunchKernelGGL(k_tb_price1, dim3(static_cast<unsigned>(nJ)), dim3(TB_WG), 0, s, mp, nblk, sl.T, d_g, d_inflist, d_st, pend, d_gu, sl.d1);
-            hipLaunchKernelGGL(k_tb_select, dim3(1), dim3(TB_WG), 0, s, nJ, sl.dJ, sl.d1, sl.statJ, sl.xJ, sl.lJ, sl.uJ, d_st);
-            hipLaunchKernelGGL(k_tb_ratio1, dim3(nblk), dim3(TB_WG), 0, s, mp, sl.T, d_xB, d_lB, d_uB, d_st, d_eta, d_part, pend);
-            hipLaunchKernelGGL(k_tb_tmax, dim3(1), dim3(TB_WG), 0, s, nblk, d_part, d_st, d_blist);
-            hipLaunchKernelGGL(k_tb_ratio, dim3(nblk), dim3(TB_WG), 0, s, mp, d_xB, d_lB, d_uB, d_st, d_eta, d_rpart);
-            hipLaunchKernelGGL(k_tb_decide, dim3(1), dim3(TB_WG), 0, s, nblk, d_rpart, sl.xJ, sl.lJ, sl.uJ, sl.statJ, d_st);
-            hipLaunchKernelGGL(k_tb_rowcopy, dim3(gridof(nJ)), dim3(TB_WG), 0, s, mp, nJ, sl.T, d_eta, d_st, pend, sl.rowbuf);
-            hipLaunchKernelGGL(k_tb_update, dim3(static_cast<unsigned>(std::min(nblk, 64))), dim3(TB_WG), 0, s, mp, d_xB, d_eta, d_st, d_blist);
-            hipLaunchKernelGGL(k_tb_post, dim3(1), dim3(TB_WG), 0, s, nJ, sl.dJ, sl.rowbuf, d_head, d_xB, d_lB, d_uB, d_cB, sl.varJ, sl.xJ, sl.lJ, sl.uJ,
-                               sl.cJ, sl.statJ, d_eta_r, d_st, sl.vbuf, sl.cap, d_pr, sl.s0, sl.sbase);
-        };
-        auto fold = [&]() { // applies the pending batch when it is nearly full, or when the run has stopped
-            const TbPend pend{sl.vbuf, d_pr, sl.s0, sl.sbase, sl.cap};
-            hipLaunchKernelGGL(k_tb_fold_begin, dim3(1), dim3(1), 0, s, d_st, 16);
-            hipLaunchKernelGGL(k_tb_fold, dim3(static_cast<unsigned>(std::min(nblk, 128)), static_cast<unsigned>((nJ + TB_FJ - 1) / TB_FJ)), dim3(TB_WG), 0, s,
-                               mp, nJ, sl.T, d_eta, d_st, pend);
-            hipLaunchKernelGGL(k_tb_fold_end, dim3(gridof(nJ)), dim3(TB_WG), 0, s, nJ, d_st, sl.s0, sl.sbase);
-            hipLaunchKernelGGL(k_tb_fold_done, dim3(1), dim3(1), 0, s, d_st);
-        };
-        int rounds = 0;
-        bool restart = false;
-        std::vector<double> hrc; // reduced costs of the structural columns under the last duals
-        for (;;) {
-            ++rounds;
-            if (nJ > 0) {
-                for (;;) {
-                    for (int k = 0; k < 16; ++k) one_pivot();
-                    fold();
-                    SX_HIP(hipMemcpyAsync(&hst, d_st, sizeof(hst), hipMemcpyDeviceToHost, s));
-                    SX_HIP(hipStreamSynchronize(s));
-                    SX_HIP(hipGetLastError());
-                    if (hst.status != 0) break;
-                }
-            } else { // nothing tracked: only the state of the basic variables decides the phase
-                hipLaunchKernelGGL(k_tb_infeas, dim3(nblk), dim3(TB_WG), 0, s, mp, d_xB, d_lB, d_uB, d_st, d_g, d_infpart);
-                hipLaunchKernelGGL(k_tb_phase, dim3(1), dim3(TB_WG), 0, s, nblk, d_infpart, d_st, d_infoff);
-                SX_HIP(hipMemcpyAsync(&hst, d_st, sizeof(hst), hipMemcpyDeviceToHost, s));
-                SX_HIP(hipStreamSynchronize(s));
-                hst.status = 1;
-            }
-            if (trace)
-                fprintf(stderr, "[sx_crossover_band]   round %d: status %d after %lld iterations (%lld pivots, %lld flips, %lld of no length), phase %d, %d "
-                                "infeasible (sum %.3e), %.1f ms so far\n", rounds, hst.status, hst.iters, hst.pivots, hst.flips, hst.degen, hst.phase,
-                        hst.n_inf, hst.sum_inf, now() - t_begin);
-            if (hst.status == 3 && hst.n_eta >= hst.cap_eta && tot_iters + hst.iters < max_iter) {
-                restart = true; // the eta file is full: factor the basis afresh
-                break;
-            }
-            if (hst.status != 1) break;
-            // ---- no tracked column prices out: duals, then every other column.  In phase 1 the cost is the
-            //      infeasibility's (g on the basic variables, nothing elsewhere)
-            const bool ph1 = hst.phase == 1;
-            SX_HIP(hipMemcpyAsync(d_vec, ph1 ? d_g : d_cB, sizeof(double) * static_cast<size_t>(mp), hipMemcpyDeviceToDevice, s));
-            const int ets = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(TB_ETS, mp / 8192)));
-            for (int64_t hi = hst.n_eta; hi > 0; hi -= TB_EB) { // blocks of TB_EB etas, the youngest first
-                const int64_t k0 = std::max<int64_t>(0, hi - TB_EB);
-                const int K = static_cast<int>(hi - k0);
-                hipLaunchKernelGGL(k_tb_etat_dots, dim3(static_cast<unsigned>(ets), static_cast<unsigned>(K)), dim3(TB_WG), 0, s, mp, d_vec, d_eta, d_eta_r, k0, d_etp);
-                hipLaunchKernelGGL(k_tb_etat_solve, dim3(1), dim3(64), 0, s, mp, ets, K, d_vec, d_eta, d_eta_r, k0, d_etp);
-            }
-            SX_TRY(ops.btran(d_vec)); // B_aug^T y = v: position space in, row space out
-            std::vector<double> yeq;
-            SX_TRY(down(s, yeq, d_vec, static_cast<size_t>(mp)));
-            SX_HIP(hipStreamSynchronize(s));
-            if (trace) fprintf(stderr, "[sx_crossover_band]   round %d: duals (eta file of %lld, transposed solves) by %.1f ms\n", rounds, (long long)hst.n_eta, now() - t_begin);
-            for (int64_t i = 0; i < m; ++i) hy[i] = yeq[eqidx[i]];
-            // reduced costs of all structural columns with these duals (the K1 walk): rc = c' - A^T y
-            SX_HIP(hipMemcpyAsync(d_tmpm, hy.data(), sizeof(double) * static_cast<size_t>(m), hipMemcpyHostToDevice, s));
-            const double *cost = c;
-            if (ph1) {
-                SX_HIP(hipMemsetAsync(d_tmpn, 0, sizeof(double) * static_cast<size_t>(n), s));
-                cost = d_tmpn;
-            }
-            SX_TRY(sx_score_columns_dev(ctx, A, d_tmpm, cost, nullptr, nullptr, nullptr, 0.0, d_rc, nullptr));
-            SX_TRY(down(s, hrc, d_rc, static_cast<size_t>(n)));
-            // who is where now
-            std::vector<int32_t> hh, hvarJ, hstatJ;
-            SX_TRY(down(s, hh, d_head, static_cast<size_t>(mp)));
-            SX_TRY(down(s, hvarJ, sl.varJ, static_cast<size_t>(nJ)));
-            SX_TRY(down(s, hstatJ, sl.statJ, static_cast<size_t>(nJ)));
-            SX_HIP(hipStreamSynchronize(s));
-            if (trace) fprintf(stderr, "[sx_crossover_band]   round %d: reduced costs by %.1f ms\n", rounds, now() - t_begin);
-            std::fill(vstat.begin(), vstat.end(), 0);
-            for (int64_t p = 0; p < mp; ++p)
-                if (hh[p] >= 0) vstat[hh[p]] = 1;
-            for (int64_t t = 0; t < nJ; ++t) vstat[hvarJ[t]] = 2;
-            std::vector<std::pair<double, int32_t>> viol;
-            for (int64_t j = 0; j < n; ++j) {
-                if (vstat[j] != 0 || hl[j] == hu[j]) continue;
-                const double d = hrc[j];
-                // a free column rests at 0 and may move either way (it loads as TB_SUP): both signs price
-                const bool free_col = std::isinf(hl[j]) && std::isinf(hu[j]);
-                if (free_col ? std::fabs(d) > opt_tol : (atup[j] ? d > opt_tol : d < -opt_tol)) viol.emplace_back(std::fabs(d), static_cast<int32_t>(j));
-            }
-            for (int64_t i = 0; i < m; ++i) { // non-basic logicals sit at 0: reduced cost -y_i, only '<' rows may move (up)
-                if (vstat[n + i] != 0 || !hlt[i]) continue;
-                const double d = -hy[i];
-                if (d < -opt_tol) viol.emplace_back(std::fabs(d), static_cast<int32_t>(n + i));
-            }
-            if (trace) fprintf(stderr, "[sx_crossover_band]   round %d (%s): %zu columns outside the tableau price out\n", rounds, ph1 ? "phase 1" : "phase 2", viol.size());
-            if (viol.empty()) {
-                if (ph1) hst.status = 101; // infeasible: no column anywhere reduces the infeasibility
-                break;
-            }
-            std::sort(viol.begin(), viol.end(), [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &bb) { return a.first > bb.first || (a.first == bb.first && a.second < bb.second); });
-            const int64_t take = std::min<int64_t>(static_cast<int64_t>(viol.size()), 2048);
-            if (nJ + take > sl.cap) { // (nothing is pending here: the run stopped, its batch was folded)
-                const int rc_ = sl.reserve(s, mp, nJ + take + std::max<int64_t>(512, nJ / 2), nJ);
-                if (rc_ != SX_OK) return rc_;
-                peak_bytes = std::max(peak_bytes, 2 * TbSlots::bytes_for(mp, nJ) + sizeof(double) * static_cast<size_t>(mp) * (EPOCH + 1));
-            }
-            std::vector<int32_t> add(static_cast<size_t>(take));
-            for (int64_t t = 0; t < take; ++t) add[t] = viol[t].second;
-            std::sort(add.begin(), add.end());
-            for (int32_t v : add)
-                if (v >= n) xlog[v - n] = 0.0;
-            SX_TRY(load_slots(nJ, add));
-            SX_TRY(build_cols(nJ, take, hst.n_eta));
-            nJ += take;
-            added_total += take;
-            hst.status = 0;
-            SX_HIP(hipMemcpyAsync(d_st, &hst, sizeof(hst), hipMemcpyHostToDevice, s)); // (status only changed; counters as read)
-            SX_HIP(hipStreamSynchronize(s));
-            if (trace) fprintf(stderr, "[sx_crossover_band]   round %d: %lld columns brought into the tableau by %.1f ms\n", rounds, (long long)take, now() - t_begin);
-        }
-        // ---------------------------------------------------------------- the epoch's end state -> host
-        std::vector<int32_t> hh, hvarJ, hstatJ;
-        std::vector<double> hxb, hxJ;
-        SX_TRY(down(s, hh, d_head, static_cast<size_t>(mp)));
-        SX_TRY(down(s, hxb, d_xB, static_cast<size_t>(mp)));
-        SX_TRY(down(s, hvarJ, sl.varJ, static_cast<size_t>(nJ)));
-        SX_TRY(down(s, hstatJ, sl.statJ, static_cast<size_t>(nJ)));
-        SX_TRY(down(s, hxJ, sl.xJ, static_cast<size_t>(nJ)));
-        SX_HIP(hipStreamSynchronize(s));
-        tot_iters += hst.iters;
-        tot_pivots += hst.pivots;
-        tot_flips += hst.flips;
-        tot_degen += hst.degen;
-        std::fill(is_basic.begin(), is_basic.end(), 0);
-        std::fill(vstat.begin(), vstat.end(), 0);
-        tracked.clear();
-        viol_max = 0.0;
-        prev_pos.assign(static_cast<size_t>(m1_all), -1);
-        for (int64_t p = 0; p < mp; ++p) {
-            const int64_t v = hh[p];
-            if (v < 0) continue;
-            is_basic[v] = 1;
-            vstat[v] = 1;
-            viol_max = std::max(viol_max, std::max(var_lo(v) - hxb[p], hxb[p] - var_up(v)));
-            if (v < n) hx[v] = hxb[p];
-            if (p < m1 && v == head[p] && old_of_new[p] >= 0) prev_pos[old_of_new[p]] = v;
-        }
-        for (int64_t t = 0; t < nJ; ++t) {
-            const int64_t v = hvarJ[t];
-            tracked.push_back(static_cast<int32_t>(v));
-            vstat[v] = hstatJ[t] == TB_SUP ? 3 : 2;
-            if (v < n) {
-                hx[v] = hxJ[t];
-                atup[v] = hstatJ[t] == TB_UPP;
-            }
-        }
-        final_status = hst.status;
-        if (restart) continue;
-        if ((hst.status == 4 || hst.status == 2) && bad_epochs < 2 && tot_iters < max_iter) { // a tiny pivot / a ray that should not be: fresh factors first
-            ++bad_epochs;
+        if (C.trace) SX_TRY(trace_basic_solution(C, lp, bs, E));
+        SX_TRY(tableau_columns(C, lp, bs, E));
+        SX_TRY(simplex_rounds(C, lp, bs, E));
+        SX_TRY(end_state(C, lp, bs, E));
+        if (E.restart) continue; // (2) the eta file is full ...
+        if ((E.hst.status == 4 || E.hst.status == 2) && C.bad_epochs < 2 && C.tot_iters < C.max_iter) { // ... or a tiny pivot / a ray that should not be: fresh factors first
+            ++C.bad_epochs;
             continue;
         }
-        if (hst.status == 1) {
-            // ---- the vertex against A itself before it is called optimal: x_B was only ever updated, y came through the eta
-            //      file -- row residuals of x (one K2 walk) and the reduced costs of the basic columns (they are in hrc).
-            //      Beyond the tolerances: factor the current basis afresh and go on from there (twice at most)
-            SX_TRY(up(s, d_tmpn, hx));
-            SX_TRY(sx_score_rows_dev(ctx, A, d_tmpn, b, nullptr, 0.0, d_tmpm, nullptr));
-            SX_TRY(down(s, hslack, d_tmpm, static_cast<size_t>(m)));
-            SX_HIP(hipStreamSynchronize(s));
-            auto row_residual = [&]() {
-                double worst = 0.0;
-                for (int64_t i = 0; i < m; ++i) {
-                    const double sc = 1.0 + std::fabs(hb[i]);
-                    const double r = hlt[i] ? std::max(-hslack[i], 0.0) : std::fabs(hslack[i]);
-                    worst = std::max(worst, r / sc);
-                }
-                return worst;
-            };
-            resid_max = row_residual();
-            if (resid_max > 1e-11) {
-                // one step of iterative refinement with the factors at hand: B delta = b - A x - s (s: the logicals'
-                // values), x_B += delta -- what thousands of updates x_B -= theta alpha left behind goes at once
-                std::vector<double> slog(static_cast<size_t>(m), 0.0), rr(static_cast<size_t>(mp), 0.0), delta;
-                for (int64_t p = 0; p < mp; ++p)
-                    if (hh[p] >= n) slog[hh[p] - n] = hxb[p];
-                for (int64_t t = 0; t < nJ; ++t)
-                    if (hvarJ[t] >= n) slog[hvarJ[t] - n] = hxJ[t];
-                for (int64_t i = 0; i < m; ++i) rr[eqidx[i]] = hslack[i] - slog[i];
-                SX_TRY(up(s, d_vec, rr));
-                SX_TRY(ftran_cols(d_vec, 1, hst.n_eta, false));
-                SX_TRY(down(s, delta, d_vec, static_cast<size_t>(mp)));
-                SX_HIP(hipStreamSynchronize(s));
-                viol_max = 0.0;
-                for (int64_t p = 0; p < mp; ++p) {
-                    const int64_t v = hh[p];
-                    if (v < 0) continue;
-                    hxb[p] += delta[p];
-                    viol_max = std::max(viol_max, std::max(var_lo(v) - hxb[p], hxb[p] - var_up(v)));
-                    if (v < n) hx[v] = hxb[p];
-                }
-                SX_TRY(up(s, d_tmpn, hx));
-                SX_TRY(sx_score_rows_dev(ctx, A, d_tmpn, b, nullptr, 0.0, d_tmpm, nullptr));
-                SX_TRY(down(s, hslack, d_tmpm, static_cast<size_t>(m)));
-                SX_HIP(hipStreamSynchronize(s));
-                const double before = resid_max;
-                resid_max = row_residual();
-                if (trace) fprintf(stderr, "[sx_crossover_band] refinement of x_B: row residual %.2e -> %.2e (relative), bound violation %.2e\n", before, resid_max, viol_max);
-            }
-            double rc_basic = 0.0;
-            if (static_cast<int64_t>(hrc.size()) == n)
-                for (int64_t j = 0; j < n; ++j)
-                    if (vstat[j] == 1) rc_basic = std::max(rc_basic, std::fabs(hrc[j]) / (1.0 + std::fabs(hc[j])));
-            if (trace) fprintf(stderr, "[sx_crossover_band] check of the vertex: row residual %.2e (relative), reduced costs of basic columns %.2e\n", resid_max, rc_basic);
-            if (resid_max > 10.0 * feas_tol || rc_basic > 10.0 * opt_tol || viol_max > 10.0 * feas_tol) {
-                if (check_epochs < 2 && tot_iters < max_iter) {
-                    ++check_epochs;
+        if (E.hst.status == 1) { // (3) a vertex that fails the check against A
+            bool ok = true;
+            SX_TRY(check_vertex(C, lp, bs, E, ok));
+            if (!ok) {
+                if (C.check_epochs < 2 && C.tot_iters < C.max_iter) {
+                    ++C.check_epochs;
                     continue;
                 }
-                final_status = 4;
+                C.final_status = 4;
             }
         }
         break;
-        } // (this epoch's geometry)
     }
-    // ------------------------------------------------------------------ outputs
-    std::vector<int8_t> vb(static_cast<size_t>(n)), cb(static_cast<size_t>(m), -1);
-    // (a non-basic free column sits at no bound: -3, the code it is read with on entry)
-    for (int64_t j = 0; j < n; ++j)
-        vb[j] = vstat[j] == 1 ? 0 : ((vstat[j] == 3 || (std::isinf(hl[j]) && std::isinf(hu[j]))) ? -3 : (atup[j] ? -2 : -1));
-    for (int64_t i = 0; i < m; ++i)
-        if (vstat[n + i] == 1) cb[i] = 0;
-    double obj = 0.0;
-    for (int64_t j = 0; j < n; ++j) obj += hc[j] * hx[j];
-    if (x_out) SX_HIP(hipMemcpyAsync(x_out, hx.data(), sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, s));
-    if (y_out) SX_HIP(hipMemcpyAsync(y_out, hy.data(), sizeof(double) * static_cast<size_t>(m), hipMemcpyHostToDevice, s));
-    if (vbasis_out) SX_HIP(hipMemcpyAsync(vbasis_out, vb.data(), static_cast<size_t>(n), hipMemcpyHostToDevice, s));
-    if (cbasis_out) SX_HIP(hipMemcpyAsync(cbasis_out, cb.data(), static_cast<size_t>(m), hipMemcpyHostToDevice, s));
-    SX_HIP(hipStreamSynchronize(s));
-    result->status = final_status == 1 ? 0 : (final_status == 101 ? 1 : final_status);
-    result->iters = tot_iters;
-    result->phase1_iters = added_total;
-    result->warm_start_used = vbasis_in ? 1 : 0;
-    result->obj = obj;
-    result->max_violation = std::max(viol_max > 0 ? viol_max : 0.0, resid_max);
-    if (trace)
-        fprintf(stderr, "[sx_crossover_band] done: status %lld, %lld iterations (%lld pivots, %lld flips, %lld of no length) in %d epochs, %lld columns added by "
-                        "pricing, objective %.12e, max violation %.2e, largest blocks %.2f GB, %.1f ms\n", (long long)result->status, tot_iters, tot_pivots, tot_flips,
-                tot_degen, epochs, (long long)added_total, obj, result->max_violation, static_cast<double>(peak_bytes) * 1e-9, now() - t_begin);
-    return SX_OK;
+    // ---- 5. outputs
+    return outputs(C, lp, bs, x_out, y_out, vbasis_out, cbasis_out, result);
 }
 
 } // namespace
