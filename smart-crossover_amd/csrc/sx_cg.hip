@@ -12,6 +12,7 @@
 // Reductions are two-stage with a fixed order: results are reproducible run to run.  The recurrence
 // and the stopping rule (||r|| < tol*||b||, tested before each iteration; legacy immediate exit when
 // ||b|| <= tol) are those of the reference's pinned scipy.
+#include "sx_graph.h"
 #include "sx_internal.h"
 #include "sx_rowblock.h"
 #include "sx_segwalk.h"
@@ -452,24 +453,18 @@ SX_API int sx_projector_std_dev(sx_ctx *ctx, const sx_matrix *A, const double *x
         // replayed; the host polls the done flag between batches.  Direct launches serve the tail and
         // are the fallback when capture is unavailable.
         const int batch = 24;
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        if (ctx->opt_graph && maxiter >= 2 * batch && getenv("SX_NO_GRAPH") == nullptr) { // (SX_NO_GRAPH: direct launches, for traces)
-            if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        SxGraphBatch graph;
+        if (maxiter >= 2 * batch && sx_graph_wanted(ctx, SX_GRAPH_HEED_NO_GRAPH_ENV)) {
+            graph.capture(s, [&]() {
                 for (int k = 0; k < batch; ++k) enqueue_iteration(k & 1);
-                if (hipStreamEndCapture(s, &graph) != hipSuccess || graph == nullptr ||
-                    hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess)
-                    exec = nullptr;
-            }
+            });
             (void)hipGetLastError();
         }
-        int rc_loop = SX_OK;
         while (launched < maxiter && !finished) {
-            if (exec && launched + batch <= maxiter) {
-                if (hipGraphLaunch(exec, s) != hipSuccess) {
+            if (graph.ready() && launched + batch <= maxiter) {
+                if (graph.launch(s) != hipSuccess) {
                     sx_set_error("hipGraphLaunch failed in the CG loop");
-                    rc_loop = SX_ERR_HIP;
-                    break;
+                    return SX_ERR_HIP;
                 }
                 launched += batch;
             } else {
@@ -480,14 +475,10 @@ SX_API int sx_projector_std_dev(sx_ctx *ctx, const sx_matrix *A, const double *x
                 hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s) != hipSuccess ||
                 hipStreamSynchronize(s) != hipSuccess) {
                 sx_set_error("CG iteration batch failed");
-                rc_loop = SX_ERR_HIP;
-                break;
+                return SX_ERR_HIP;
             }
             finished = host.done != 0;
         }
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (rc_loop != SX_OK) return rc_loop;
     }
     SX_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
     SX_HIP(hipStreamSynchronize(s));

@@ -92,7 +92,8 @@ struct sx_ctx {
     // tuning knobs (sx_ctx_set_option); defaults are the measured best on MI355X
     int opt_xcd_swizzle = 1; // XCD-contiguous block -> tile map
     int opt_window = -1;     // LDS operand window of the column walk: -1 auto, 0 off, 1/2/4/8 tiles per load
-    int opt_graph = 1;       // replay the CG iteration batch as a hipGraph
+    int opt_graph = 1;       // replay iteration batches as hipGraphs: CG, first-order LP stage (K16p), dense simplex (K16) and
+                             // both Sinkhorns; 0: direct launches in all five (sx_graph.h holds what else each loop heeds)
     int opt_spx_defer = -1;  // K16 basis inverse: -1 auto, 0 rank-one update per pivot, 1 rank-32 update per batch
     int opt_rowblock = -1;   // column-blocked row layout of the row walk: -1 auto, 0 off, 1 whenever possible
     int opt_spx_check = 2048; // K16: pivots between two checks of A x + s = b (drift of the explicit inverse)
@@ -134,20 +135,35 @@ int sx_reserve3(sx_ctx *ctx, size_t bytes); // ensure ctx->ws3 holds >= bytes
 
 // Device temporaries of one call carved out of ctx->ws3 (reserved once for the call's upper bound): a network solve
 // needs 25-45 arrays, and hipMalloc / hipFree cost 50-100 us apiece -- more than a small solve itself.  What does
-// not fit falls back on hipMalloc and is freed with the arena.
+// not fit falls back on hipMalloc and is freed with the arena.  own(): the arena carves a block of its own instead, freed
+// with it -- the dense simplex, whose m x m inverse must not stay resident in the context between calls.
 struct sx_arena {
     sx_ctx *ctx;
+    char *block = nullptr; // own(); nullptr: ctx->ws3
+    size_t block_bytes = 0;
     size_t off = 0;
     std::vector<void *> extra;
     explicit sx_arena(sx_ctx *c) : ctx(c) {}
+    sx_arena(const sx_arena &) = delete;
+    sx_arena &operator=(const sx_arena &) = delete;
     ~sx_arena() {
         for (void *q : extra) (void)sx_dfree(q);
+    }
+    int own(size_t bytes) { // before the first get
+        void *d = nullptr;
+        SX_HIP(sx_dmalloc(&d, bytes));
+        extra.push_back(d);
+        block = static_cast<char *>(d);
+        block_bytes = bytes;
+        off = 0;
+        return SX_OK;
     }
     template <class T>
     int get(size_t count, T **out) {
         const size_t need = (sizeof(T) * (count ? count : 1) + 255) & ~static_cast<size_t>(255);
-        if (ctx->ws3 && off + need <= ctx->ws3_bytes) {
-            *out = reinterpret_cast<T *>(static_cast<char *>(ctx->ws3) + off);
+        char *base = block ? block : static_cast<char *>(ctx->ws3);
+        if (base && off + need <= (block ? block_bytes : ctx->ws3_bytes)) {
+            *out = reinterpret_cast<T *>(base + off);
             off += need;
             return SX_OK;
         }

@@ -19,6 +19,7 @@
 // one status word every few replays.  No atomics, fixed reduction orders: run-to-run reproducible.
 //
 // Sign convention as everywhere in this library: reduced cost = c - A^T y, dual of a '<' row <= 0.
+#include "sx_graph.h"
 #include "sx_internal.h"
 #include "sx_segwalk.h"
 
@@ -517,39 +518,17 @@ SX_API int sx_pdlp_dev(sx_ctx *ctx, const sx_matrix *A, const double *b, const d
         hipLaunchKernelGGL(k_pd_advance, dim3(1), dim3(1), 0, s, st, PD_PERIOD, 0);
     };
     // ---- one hipGraph per period of 64 iterations (+ check, decision, restart)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool use_graph = ctx->opt_graph != 0 && getenv("SX_NO_GRAPH") == nullptr &&
-                     (getenv("ROCP_TOOL_LIBRARIES") == nullptr || getenv("SX_GRAPH_UNDER_PROFILER") != nullptr);
-    // (rocprofv3 --kernel-trace faults on graph replay: profiles/r03/hipgraph_rocprofv3.md, frames named in profiles/r04/hipgraph_frames.md;
-    //  SX_GRAPH_UNDER_PROFILER=1 keeps the graph path there -- to reproduce the fault, not to measure)
-    if (use_graph) {
+    SxGraphBatch graph;
+    if (sx_graph_wanted(ctx, SX_GRAPH_HEED_NO_GRAPH_ENV | SX_GRAPH_HEED_PROFILER | SX_GRAPH_HEED_PROFILER_OVERRIDE)) {
         SX_HIP(hipStreamSynchronize(s));
-        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            period();
-            if (hipStreamEndCapture(s, &graph) != hipSuccess || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-                use_graph = false;
-                (void)hipGetLastError();
-            }
-        } else {
-            use_graph = false;
-            (void)hipGetLastError();
-        }
+        graph.capture(s, period);
     }
-    struct GraphGuard {
-        hipGraph_t &g;
-        hipGraphExec_t &e;
-        ~GraphGuard() {
-            if (e) (void)hipGraphExecDestroy(e);
-            if (g) (void)hipGraphDestroy(g);
-        }
-    } gguard{graph, exec};
     const int64_t periods = max_iter / PD_PERIOD;
     const int poll = getenv("SX_PDLP_POLL") ? std::max(1, atoi(getenv("SX_PDLP_POLL"))) : 8; // periods enqueued between two looks at the state
     for (int64_t p = 0; p < periods;) {
         const int64_t upto = std::min<int64_t>(p + poll, periods);
         for (; p < upto; ++p) {
-            if (use_graph) SX_HIP(hipGraphLaunch(exec, s));
+            if (graph.ready()) SX_HIP(graph.launch(s));
             else period();
         }
         SX_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));

@@ -46,25 +46,26 @@
 // Multi-GPU note: with columns sharded, `price` partials are per rank and the selection becomes the
 // all-gather + lexicographic min of smart_crossover/distributed.py (one small exchange per pivot);
 // this file implements the single-device solver.
+#include "sx_graph.h"
 #include "sx_internal.h"
-
 #include "sx_segwalk.h"
+#include "sx_simplex_plan.h"
 
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <unordered_map>
 #include <vector>
 
 namespace {
 
 constexpr int SPX_CHUNK = 4096;
-constexpr int SPX_GRID = 1024;   // price workgroups (= partials) at most
+constexpr int SPX_GRID = sx_spx_plan::GRID; // price workgroups (= partials) at most
 constexpr double PIV_TOL = 1e-9; // smallest |pivot| accepted
 constexpr int BLAND_AFTER = 100;
-constexpr int SPX_DEFER = 64;    // pivots whose inverse updates are held back and folded in together: the fold moves
-                                 // 16 m^2 bytes, 46 % of a pivot at m = 2e4 with a batch of 32
+constexpr int SPX_DEFER = sx_spx_plan::DEFER; // pivots whose inverse updates are held back and folded in together: the fold
+                                 // moves 16 m^2 bytes, 46 % of a pivot at m = 2e4 with a batch of 32
+static_assert(SX_WG == sx_spx_plan::WG, "the plan's grids assume the walks' workgroup");
 constexpr int SPX_REG = 32;      // of the pending columns, those a lane requests before the entering column is known
 
 // ST_FREE: non-basic and not at a bound -- a free variable at 0, or a *superbasic* one at the interior value
@@ -85,6 +86,7 @@ struct SpxState {
     int dvx_on, dvx_p;       // last step changed the basis; variable that left it
     double dvx_alpha, dvx_wq; // its pivot element; weight of the variable that entered
 };
+static_assert(sizeof(SpxState) <= 256, "one 256-byte piece of the arena (sx_simplex_plan.h: arena_bytes)");
 
 struct Spx {
     int64_t m, n;
@@ -718,7 +720,7 @@ __global__ __launch_bounds__(SX_WG) void k_spx_rho_update(Spx P, int pending, in
 // Binv[i,k] -= sum_s E_s[i] R_s[k] (in pivot order, one fma per pair: the same arithmetic as `cnt` rank-one
 // updates, with 1/cnt of their HBM traffic).  A workgroup owns 256 rows x FOLD_COLS columns: each lane keeps
 // its row of E in registers, the R tile sits in LDS and is read as a broadcast.
-constexpr int FOLD_COLS = 64;
+constexpr int FOLD_COLS = sx_spx_plan::FOLD_COLS;
 __global__ __launch_bounds__(SX_WG) void k_spx_fold(Spx P, int cnt, int col_tiles) {
     __shared__ double rt[SPX_DEFER][FOLD_COLS];
     __shared__ int any_live;
@@ -794,7 +796,7 @@ __global__ __launch_bounds__(SX_WG) void k_spx_fold_mask(Spx P, int cnt) {
 // scalar kernel's by the order of the 64 products inside a tile row (the MFMA's own), within the tests' tolerance.
 // NOT the default: see the measurement where it is selected.
 typedef double spx_v4d __attribute__((ext_vector_type(4)));
-constexpr int FM_KT = 64, FM_IC = 16; // column tiles x row chunks of one super-block of workgroups
+constexpr int FM_KT = sx_spx_plan::FM_KT, FM_IC = sx_spx_plan::FM_IC; // column tiles x row chunks of one super-block of workgroups
 
 typedef double spx_v2d __attribute__((ext_vector_type(2)));
 
@@ -1216,42 +1218,6 @@ inline unsigned grid1d(int64_t n, int64_t cap = 4096) {
     return static_cast<unsigned>(g < 1 ? 1 : g);
 }
 
-// per-solve device buffers: one arena allocation carved into 256-byte aligned pieces (a solve used to
-// make ~20 hipMalloc / hipFree pairs, milliseconds that a short warm-started re-solve does not have);
-// requests beyond the arena fall back to allocations of their own
-struct DevBufs {
-    std::vector<void *> p;
-    char *arena = nullptr;
-    size_t arena_bytes = 0, used = 0;
-    ~DevBufs() {
-        for (void *q : p)
-            if (q) (void)sx_dfree(q);
-    }
-    int reserve(size_t bytes) {
-        void *d = nullptr;
-        SX_HIP(sx_dmalloc(&d, bytes));
-        p.push_back(d);
-        arena = static_cast<char *>(d);
-        arena_bytes = bytes;
-        used = 0;
-        return SX_OK;
-    }
-    template <class T>
-    int get(size_t count, T **out) {
-        const size_t want = (sizeof(T) * (count ? count : 1) + 255) & ~static_cast<size_t>(255);
-        if (arena && used + want <= arena_bytes) {
-            *out = reinterpret_cast<T *>(arena + used);
-            used += want;
-            return SX_OK;
-        }
-        void *d = nullptr;
-        SX_HIP(sx_dmalloc(&d, want));
-        p.push_back(d);
-        *out = static_cast<T *>(d);
-        return SX_OK;
-    }
-};
-
 // install a basis whose inverse is already in P.Binv: every logical non-basic first, then the head
 __global__ __launch_bounds__(SX_WG) void k_spx_logicals_out(Spx P) {
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * SX_WG + threadIdx.x; i < P.m;
@@ -1307,109 +1273,115 @@ SX_API int sx_simplex_session_destroy(sx_simplex_session *session) {
     return SX_OK;
 }
 
-static int spx_solve(sx_ctx *ctx, sx_simplex_session *session, const sx_matrix *A, const double *b, const double *c,
-                     const double *l, const double *u, const uint8_t *row_is_lt, const int8_t *vbasis_in,
-                     const int8_t *cbasis_in, const int64_t *col_ids, const double *x_start, int64_t max_iter,
-                     double feas_tol, double opt_tol, double *x_out, double *y_out, int8_t *vbasis_out,
-                     int8_t *cbasis_out, sx_simplex_result *result);
+// ------------------------------------------------------------------------------------------------ the driver
+// A solve is a list of stages over two records: what the caller asked for (SpxCall) and what the solve has built and
+// learnt so far (SpxRun).  The host arithmetic between the launches is sx_simplex_plan.h.
+namespace {
 
-SX_API int sx_simplex_solve_dev(sx_ctx *ctx, const sx_matrix *A, const double *b, const double *c, const double *l,
-                                const double *u, const uint8_t *row_is_lt, const int8_t *vbasis_in,
-                                const int8_t *cbasis_in, int64_t max_iter, double feas_tol, double opt_tol,
-                                double *x_out, double *y_out, int8_t *vbasis_out, int8_t *cbasis_out,
-                                sx_simplex_result *result) {
-    return spx_solve(ctx, nullptr, A, b, c, l, u, row_is_lt, vbasis_in, cbasis_in, nullptr, nullptr, max_iter, feas_tol,
-                     opt_tol, x_out, y_out, vbasis_out, cbasis_out, result);
+namespace plan = sx_spx_plan;
+
+struct SpxCall {
+    sx_ctx *ctx;
+    sx_simplex_session *session; // nullptr: the inverse lives for this call only
+    const sx_matrix *A;
+    const double *b, *c, *l, *u;
+    const uint8_t *row_is_lt;
+    const int8_t *vbasis_in, *cbasis_in; // warm basis in the reference's codes (both or neither)
+    const int64_t *col_ids;              // stable ids of the columns: what a session matches its inverse by
+    const double *x_start;               // crossover: the point the first basic solution has to be
+    int64_t max_iter;
+    double feas_tol, opt_tol;
+    double *x_out, *y_out;
+    int8_t *vbasis_out, *cbasis_out;
+    sx_simplex_result *result;
+};
+
+struct SpxRun {
+    explicit SpxRun(sx_ctx *ctx) : s(ctx->stream), mem(ctx) {}
+    Spx P{}; // s_keep stays nullptr here: the stages that install a basis pass their own (spx_install)
+    hipStream_t s;
+    unsigned gN = 0, gM = 0, gMM = 0; // per variable, per row, per entry of the inverse
+    int gP = 0, gL = 0, gR = 0;       // pricing: column tiles + logicals; row tiles
+    bool defer = false, devex = false, fold_mfma = false, trace = false;
+    double *s_keep_buf = nullptr, *meas = nullptr;
+    unsigned long long *resid_dev = nullptr;
+    int8_t *vb_now = nullptr, *cb_now = nullptr; // the current basis in the reference's codes (re-inversion)
+    sx_arena mem;
+    // a batch of 64 pivots = 192 small launches (+ the fold) with fixed arguments: captured into a hipGraph and
+    // replayed (pivots are launch-bound for small m); direct launches are the fallback.  Capturing and
+    // instantiating costs milliseconds, more than a short warm-started re-solve takes altogether, so the
+    // graph is only built once a solve has gone through GRAPH_AFTER pivots by direct launches.
+    SxGraphBatch graph;
+    bool graph_tried = false;
+    SpxState host{};
+    double host_meas[3] = {0, 0, 0}; // k_spx_measure: worst violation, infeasibility left in phase 1, objective
+    std::vector<int8_t> vb_in;       // host copy of vbasis_in
+    bool warm = false, reused = false;
+    int64_t n_reinvert = 0, direct_pivots = 0 /* over both phases */, phase1_iters = 0;
+    std::chrono::steady_clock::time_point t_enter;
+    double t_setup_ms = 0.0, t_crash_ms = 0.0, t_start_ms = 0.0; // SX_SPX_TRACE
+};
+constexpr int64_t GRAPH_AFTER = 4096; // with 3 launches per pivot replay only insures against a slow host
+
+Spx keeping(const Spx &P, double *s_keep) {
+    Spx Q = P;
+    Q.s_keep = s_keep;
+    return Q;
 }
 
-SX_API int sx_simplex_solve_session_dev(sx_ctx *ctx, sx_simplex_session *session, const sx_matrix *A, const double *b,
-                                        const double *c, const double *l, const double *u, const uint8_t *row_is_lt,
-                                        const int8_t *vbasis_in, const int8_t *cbasis_in, const int64_t *col_ids,
-                                        int64_t max_iter, double feas_tol, double opt_tol, double *x_out,
-                                        double *y_out, int8_t *vbasis_out, int8_t *cbasis_out,
-                                        sx_simplex_result *result) {
-    return spx_solve(ctx, session, A, b, c, l, u, row_is_lt, vbasis_in, cbasis_in, col_ids, nullptr, max_iter, feas_tol,
-                     opt_tol, x_out, y_out, vbasis_out, cbasis_out, result);
+double spx_ms_since_enter(const SpxRun &run, bool drained) {
+    if (drained) (void)hipStreamSynchronize(run.s);
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - run.t_enter).count();
 }
 
-SX_API int sx_simplex_crossover_dev(sx_ctx *ctx, const sx_matrix *A, const double *b, const double *c, const double *l,
-                                    const double *u, const uint8_t *row_is_lt, const int8_t *vbasis_in,
-                                    const int8_t *cbasis_in, const double *x_start, int64_t max_iter, double feas_tol,
-                                    double opt_tol, double *x_out, double *y_out, int8_t *vbasis_out,
-                                    int8_t *cbasis_out, sx_simplex_result *result) {
-    SX_REQUIRE(x_start != nullptr && vbasis_in != nullptr && cbasis_in != nullptr,
-               "sx_simplex_crossover_dev needs a starting point and a basis guess");
-    return spx_solve(ctx, nullptr, A, b, c, l, u, row_is_lt, vbasis_in, cbasis_in, nullptr, x_start, max_iter, feas_tol,
-                     opt_tol, x_out, y_out, vbasis_out, cbasis_out, result);
-}
-
-static int spx_solve(sx_ctx *ctx, sx_simplex_session *session, const sx_matrix *A, const double *b, const double *c,
-                     const double *l, const double *u, const uint8_t *row_is_lt, const int8_t *vbasis_in,
-                     const int8_t *cbasis_in, const int64_t *col_ids, const double *x_start, int64_t max_iter,
-                     double feas_tol, double opt_tol, double *x_out, double *y_out, int8_t *vbasis_out,
-                     int8_t *cbasis_out, sx_simplex_result *result) {
-    SX_ENTER(ctx);
-    SX_REQUIRE(session == nullptr || session->ctx == ctx, "the session belongs to another context");
-    SX_REQUIRE(A && b && c && l && u && row_is_lt && result, "NULL argument");
-    SX_REQUIRE(A->csr_ptr && A->csc_ptr, "the simplex needs both layouts of A");
-    SX_REQUIRE((vbasis_in == nullptr) == (cbasis_in == nullptr), "vbasis_in and cbasis_in go together");
-    memset(result, 0, sizeof(*result));
-    const int64_t m = A->m, n = A->n, N = n + m;
-    {   // the basis inverse is an explicit dense m x m matrix: it has to fit the HBM that is free now
-        size_t free_b = 0, total_b = 0;
-        SX_HIP(hipMemGetInfo(&free_b, &total_b));
-        const double need = 8.0 * static_cast<double>(m) * static_cast<double>(m) + 600.0 * static_cast<double>(m) +
-                            40.0 * static_cast<double>(N);
-        const bool have_inverse = session && session->m == m && session->Binv != nullptr;
-        if (!have_inverse && need > 0.9 * static_cast<double>(free_b)) {
-            sx_set_error("sx_simplex_solve: the dense basis inverse of %lld rows needs %.1f GB, %.1f GB of HBM are free",
-                         (long long)m, need / 1e9, static_cast<double>(free_b) / 1e9);
-            return SX_ERR_UNSUPPORTED;
-        }
-    }
-    if (max_iter <= 0) max_iter = 50 * (m + n) + 1000;
-    hipStream_t s = ctx->stream;
-    const auto t_enter = std::chrono::steady_clock::now();
+void spx_options(const SpxCall &call, SpxRun &run) {
+    const int64_t m = call.A->m;
     // measured (profiles/r01/spx_bench.txt): holding the updates back is as fast as the rank-one update per
     // pivot at 200-1000 rows and 1.3x / 2.2x faster at 2000 / 4000, so "auto" means on
-    const bool defer = ctx->opt_spx_defer != 0;
-    const bool devex = ctx->opt_spx_pricing != 0;
+    run.defer = call.ctx->opt_spx_defer != 0;
+    run.devex = call.ctx->opt_spx_pricing != 0;
+    // large inverses fold on the matrix cores (k_spx_fold_mfma), small ones by the scalar kernel in pivot order
+    static const char *blas_env = getenv("SX_SPX_BLAS"); // "0": the scalar fold kernel at every size (A/B runs)
+    // measured at m = 2e4 (tools/fold_bench.py, profiles/r03/spx_fold.md): scalar kernel 1.76 ms per fold, this
+    // matrix-core kernel 2.2 ms, the vendor DGEMM it replaced 1.46 ms -- so the scalar kernel is the default and the
+    // matrix-core one is kept for the record (and its tests) behind SX_SPX_FOLD_MFMA_MIN = rows from which it runs
+    const char *fm_env = getenv("SX_SPX_FOLD_MFMA_MIN");
+    const int64_t fm_min = fm_env ? atoll(fm_env) : INT64_MAX;
+    run.fold_mfma = run.defer && m >= fm_min && !(blas_env && blas_env[0] == '0');
+    run.trace = getenv("SX_SPX_TRACE") != nullptr; // stderr: where the wall time of a solve goes
+}
 
-    DevBufs mem;
-    {
-        // everything below except a session-less inverse: 34 B per variable, 44 B per row, pricing partials
-        const size_t um = static_cast<size_t>(m), uN = static_cast<size_t>(N);
-        size_t bytes = 34 * uN + 56 * um + 24 * (static_cast<size_t>(SPX_GRID) + um / 64 + 64) + 32 * 256 + 4096;
-        if (!session) bytes += sizeof(double) * um * um + 256;
-        if (defer) bytes += 2 * sizeof(double) * um * SPX_DEFER + 1024;
-        bytes += 32 * (um / SX_WG + 2) + 1024; // ratio candidates, tickets
-        if (devex) bytes += sizeof(double) * uN + 256;
-        SX_TRY(mem.reserve(bytes));
-    }
-    Spx P;
+// every device array of the solve, carved from one block (a solve used to make ~20 hipMalloc / hipFree pairs,
+// milliseconds that a short warm-started re-solve does not have); a session's inverse is its own and outlives the call
+int spx_allocate(const SpxCall &call, SpxRun &run) {
+    sx_ctx *ctx = call.ctx;
+    sx_simplex_session *session = call.session;
+    const sx_matrix *A = call.A;
+    Spx &P = run.P;
+    hipStream_t s = run.s;
+    sx_arena &mem = run.mem;
+    const int64_t m = A->m, n = A->n, N = n + m;
+    SX_TRY(mem.own(plan::arena_bytes(m, N, session != nullptr, run.defer, run.devex, SPX_GRID)));
     P.m = m;
     P.n = n;
-    P.row_lt = row_is_lt;
-    P.c_true = c;
-    P.l_true = l;
-    P.u_true = u;
+    P.row_lt = call.row_is_lt;
+    P.c_true = call.c;
+    P.l_true = call.l;
+    P.u_true = call.u;
     SX_TRY(mem.get(static_cast<size_t>(N), &P.status));
     SX_TRY(mem.get(static_cast<size_t>(N), &P.relaxed));
     SX_TRY(mem.get(static_cast<size_t>(N), &P.lo));
     SX_TRY(mem.get(static_cast<size_t>(N), &P.up));
     SX_TRY(mem.get(static_cast<size_t>(N), &P.cost));
     SX_TRY(mem.get(static_cast<size_t>(N), &P.x));
-    P.w = nullptr;
-    if (devex) SX_TRY(mem.get(static_cast<size_t>(N), &P.w));
+    if (run.devex) SX_TRY(mem.get(static_cast<size_t>(N), &P.w));
     SX_TRY(mem.get(static_cast<size_t>(m), &P.head));
     SX_TRY(mem.get(static_cast<size_t>(m), &P.y));
     SX_TRY(mem.get(static_cast<size_t>(m), &P.d));
     SX_TRY(mem.get(static_cast<size_t>(m), &P.rho));
     SX_TRY(mem.get(static_cast<size_t>(m), &P.rhs));
-    double *s_keep_buf = nullptr;
-    SX_TRY(mem.get(static_cast<size_t>(m), &s_keep_buf));
-    P.s_keep = nullptr;
-    if (session) { // the inverse outlives the call
+    SX_TRY(mem.get(static_cast<size_t>(m), &run.s_keep_buf));
+    if (session) {
         if (session->m != m || session->Binv == nullptr) {
             if (session->Binv) SX_HIP(sx_dfree(session->Binv));
             session->Binv = nullptr;
@@ -1428,9 +1400,7 @@ static int spx_solve(sx_ctx *ctx, sx_simplex_session *session, const sx_matrix *
     } else {
         SX_TRY(mem.get(static_cast<size_t>(m) * static_cast<size_t>(m), &P.Binv));
     }
-    P.E = P.R = nullptr;
-    P.er = nullptr;
-    if (defer) {
+    if (run.defer) {
         SX_TRY(mem.get(static_cast<size_t>(m) * SPX_DEFER, &P.E));
         SX_TRY(mem.get(static_cast<size_t>(m) * SPX_DEFER, &P.R));
         SX_TRY(mem.get(static_cast<size_t>(SPX_DEFER), &P.er));
@@ -1447,380 +1417,394 @@ static int spx_solve(sx_ctx *ctx, sx_simplex_session *session, const sx_matrix *
         SX_HIP(hipMemsetAsync(P.tickets, 0, 2 * sizeof(unsigned), s));
     }
     SX_TRY(mem.get(1, &P.st));
-    const int gP = static_cast<int>(A->n_csc_tiles < SPX_GRID ? (A->n_csc_tiles > 0 ? A->n_csc_tiles : 1) : SPX_GRID);
-    const int gL = static_cast<int>(grid1d(m, 64));
-    SX_TRY(mem.get(static_cast<size_t>(gP + gL), &P.p_score));
-    SX_TRY(mem.get(static_cast<size_t>(gP + gL), &P.p_rc));
-    SX_TRY(mem.get(static_cast<size_t>(gP + gL), &P.p_idx));
-    double *meas = nullptr;
-    SX_TRY(mem.get(3, &meas));
-    P.b = const_cast<double *>(b);
+    run.gP = static_cast<int>(A->n_csc_tiles < SPX_GRID ? (A->n_csc_tiles > 0 ? A->n_csc_tiles : 1) : SPX_GRID);
+    run.gL = static_cast<int>(grid1d(m, 64));
+    SX_TRY(mem.get(static_cast<size_t>(run.gP + run.gL), &P.p_score));
+    SX_TRY(mem.get(static_cast<size_t>(run.gP + run.gL), &P.p_rc));
+    SX_TRY(mem.get(static_cast<size_t>(run.gP + run.gL), &P.p_idx));
+    SX_TRY(mem.get(3, &run.meas));
+    P.b = const_cast<double *>(call.b);
     SX_HIP(hipMemsetAsync(P.st, 0, sizeof(SpxState), s));
+    run.gN = grid1d(N);
+    run.gM = grid1d(m);
+    run.gMM = grid1d(m * m, 8192);
+    run.gR = static_cast<int>(A->n_csr_tiles < SPX_GRID ? (A->n_csr_tiles > 0 ? A->n_csr_tiles : 1) : SPX_GRID);
+    SX_TRY(mem.get(2, &run.resid_dev));
+    SX_TRY(mem.get(static_cast<size_t>(n), &run.vb_now));
+    SX_TRY(mem.get(static_cast<size_t>(m), &run.cb_now));
+    return SX_OK;
+}
 
-    const unsigned gN = grid1d(N), gM = grid1d(m), gMM = grid1d(m * m, 8192);
-    const int gR = static_cast<int>(A->n_csr_tiles < SPX_GRID ? (A->n_csr_tiles > 0 ? A->n_csr_tiles : 1) : SPX_GRID);
+// x_B = Binv (b - N x_N) from scratch, and y = Binv^T c_B with it
+void spx_refresh(const SpxCall &call, const SpxRun &run, bool with_y) {
+    const sx_matrix *A = call.A;
+    const int64_t m = run.P.m;
+    hipLaunchKernelGGL(k_spx_rhs, dim3(run.gR), dim3(SX_WG), 0, run.s, run.P, A->csr_tiles, A->n_csr_tiles, A->csr_ptr,
+                       A->csr_idx, A->csr_val);
+    hipLaunchKernelGGL(k_spx_xb, dim3(grid1d(m * 4, 2048)), dim3(1024), 0, run.s, run.P); // one workgroup per 64 rows
+    if (with_y) hipLaunchKernelGGL(k_spx_btran, dim3(grid1d(m * 64)), dim3(SX_WG), 0, run.s, run.P);
+}
 
-    auto refresh = [&](bool with_y) {
-        hipLaunchKernelGGL(k_spx_rhs, dim3(gR), dim3(SX_WG), 0, s, P, A->csr_tiles, A->n_csr_tiles, A->csr_ptr,
-                           A->csr_idx, A->csr_val);
-        hipLaunchKernelGGL(k_spx_xb, dim3(grid1d(m * 4, 2048)), dim3(1024), 0, s, P); // one workgroup per 64 rows
-        if (with_y) hipLaunchKernelGGL(k_spx_btran, dim3(grid1d(m * 64)), dim3(SX_WG), 0, s, P);
-    };
-    const int fold_col_tiles = static_cast<int>((m + FOLD_COLS - 1) / FOLD_COLS);
-    const unsigned fold_grid = static_cast<unsigned>(((m + SX_WG - 1) / SX_WG) * fold_col_tiles);
-    // large inverses fold on the matrix cores (k_spx_fold_mfma), small ones by the scalar kernel in pivot order
-    static const char *blas_env = getenv("SX_SPX_BLAS"); // "0": the scalar fold kernel at every size (A/B runs)
-    // measured at m = 2e4 (tools/fold_bench.py, profiles/r03/spx_fold.md): scalar kernel 1.76 ms per fold, this
-    // matrix-core kernel 2.2 ms, the vendor DGEMM it replaced 1.46 ms -- so the scalar kernel is the default and the
-    // matrix-core one is kept for the record (and its tests) behind SX_SPX_FOLD_MFMA_MIN = rows from which it runs
-    const char *fm_env = getenv("SX_SPX_FOLD_MFMA_MIN");
-    const int64_t fm_min = fm_env ? atoll(fm_env) : INT64_MAX;
-    const bool fold_mfma = defer && m >= fm_min && !(blas_env && blas_env[0] == '0');
-    const int64_t fm_nkt = (m + 15) / 16, fm_nic = (m + 255) / 256;
-    const unsigned fm_grid = static_cast<unsigned>(((fm_nkt + FM_KT - 1) / FM_KT) * ((fm_nic + FM_IC - 1) / FM_IC) * FM_KT * FM_IC);
-    auto fold = [&](int cnt) {
-        if (fold_mfma) {
-            hipLaunchKernelGGL(k_spx_fold_mask, dim3(gM, SPX_DEFER), dim3(SX_WG), 0, s, P, cnt); // empty slots: zero columns
-            hipLaunchKernelGGL(k_spx_fold_mfma, dim3(fm_grid), dim3(SX_WG), 0, s, P, fm_nkt, fm_nic);
-            return;
-        }
-        hipLaunchKernelGGL(k_spx_fold, dim3(fold_grid), dim3(SX_WG), 0, s, P, cnt, fold_col_tiles);
-    };
-    double host_meas[3] = {0, 0, 0};
-    auto measure = [&]() -> int {
-        hipLaunchKernelGGL(k_spx_measure, dim3(1), dim3(1024), 0, s, P, meas);
-        SX_HIP(hipMemcpyAsync(host_meas, meas, sizeof(host_meas), hipMemcpyDeviceToHost, s));
-        SX_HIP(hipStreamSynchronize(s));
-        return SX_OK;
-    };
-    auto cold_start = [&](int use_cost) {
-        hipLaunchKernelGGL(k_spx_init, dim3(gN), dim3(SX_WG), 0, s, P, l, u, c, use_cost);
-        hipLaunchKernelGGL(k_spx_identity, dim3(gMM), dim3(SX_WG), 0, s, P);
-    };
-
-    // ---- helpers of the starting basis and of numerical hygiene
-    unsigned long long *resid_dev = nullptr;
-    SX_TRY(mem.get(2, &resid_dev));
-    int8_t *vb_now = nullptr, *cb_now = nullptr; // the current basis in the reference's codes (re-inversion)
-    SX_TRY(mem.get(static_cast<size_t>(n), &vb_now));
-    SX_TRY(mem.get(static_cast<size_t>(m), &cb_now));
-    // max_i |b_i - (A x)_i - s_i| / (1 + max |b|): what the explicit inverse has drifted by
-    auto residual = [&](double *rel) -> int {
-        SX_HIP(hipMemsetAsync(resid_dev, 0, 2 * sizeof(unsigned long long), s));
-        hipLaunchKernelGGL(k_spx_residual, dim3(gR), dim3(SX_WG), 0, s, P, A->csr_tiles, A->n_csr_tiles, A->csr_ptr,
-                           A->csr_idx, A->csr_val, resid_dev);
-        unsigned long long h[2] = {0, 0};
-        SX_HIP(hipMemcpyAsync(h, resid_dev, sizeof(h), hipMemcpyDeviceToHost, s));
-        SX_HIP(hipStreamSynchronize(s));
-        double worst, bmax;
-        memcpy(&worst, &h[0], sizeof(double));
-        memcpy(&bmax, &h[1], sizeof(double));
-        *rel = worst / (1.0 + bmax);
-        return SX_OK;
-    };
-    const double resid_tol = feas_tol;
-    // pivot the structural columns flagged basic in vb_host (n codes) into the all-logical basis (identity
-    // inverse): for each column the largest available pivot among the rows still held by a logical, rows whose
-    // logical the target basis keeps (cb_dev code 0) only as a last resort; a column without a usable row stays
-    // non-basic
-    auto install = [&](const std::vector<int8_t> &vb_host, const int8_t *cb_dev) {
-        int slot = 0;
-        for (int64_t j = 0; j < n; ++j) {
-            if (vb_host[static_cast<size_t>(j)] != ST_BASIC) continue;
-            hipLaunchKernelGGL(k_spx_ftran, dim3(gM), dim3(SX_WG), 0, s, P, A->csc_ptr, A->csc_idx, A->csc_val,
-                               static_cast<int>(j), 0, defer ? slot : 0, cb_dev);
-            hipLaunchKernelGGL(k_spx_rho, dim3(gM), dim3(SX_WG), 0, s, P, static_cast<int>(j), defer ? slot : 0,
-                               defer ? slot : -1);
-            if (!defer) {
-                hipLaunchKernelGGL(k_spx_update_binv, dim3(gMM), dim3(SX_WG), 0, s, P);
-            } else if (++slot == SPX_DEFER) {
-                fold(slot);
-                slot = 0;
-            }
-        }
-        if (defer && slot > 0) fold(slot);
-        hipLaunchKernelGGL(k_spx_reset_state, dim3(1), dim3(1), 0, s, P);
-    };
-    // rebuild the inverse of the CURRENT basis from its columns (the running inverse has only ever seen
-    // rank-one updates and drifts): all logicals back in, identity, the basic structurals pivoted in again
-    int64_t n_reinvert = 0;
-    std::vector<int8_t> vb_host;
-    auto reinvert = [&]() -> int {
-        hipLaunchKernelGGL(k_spx_export, dim3(gN), dim3(SX_WG), 0, s, P, static_cast<double *>(nullptr),
-                           static_cast<double *>(nullptr), vb_now, cb_now);
-        vb_host.resize(static_cast<size_t>(n));
-        SX_HIP(hipMemcpyAsync(vb_host.data(), vb_now, static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
-        SX_HIP(hipStreamSynchronize(s));
-        P.s_keep = s_keep_buf; // nothing moves: displaced logicals keep the value they have now
-        hipLaunchKernelGGL(k_spx_logical_basis, dim3(gN), dim3(SX_WG), 0, s, P);
-        hipLaunchKernelGGL(k_spx_identity, dim3(gMM), dim3(SX_WG), 0, s, P);
-        if (defer) SX_HIP(hipMemsetAsync(P.er, 0xff, sizeof(int32_t) * SPX_DEFER, s));
-        install(vb_host, cb_now);
-        P.s_keep = nullptr;
-        ++n_reinvert;
-        SX_HIP(hipGetLastError());
-        return SX_OK;
-    };
-
-    // ---- starting basis
-    bool warm = false, reused = false;
-    std::vector<int8_t> vb;
-    if (vbasis_in) {
-        vb.resize(static_cast<size_t>(n));
-        SX_HIP(hipMemcpyAsync(vb.data(), vbasis_in, static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
-        SX_HIP(hipStreamSynchronize(s));
+// the first cnt pending updates of a batch into the inverse
+void spx_fold(const SpxRun &run, const Spx &P, int cnt) {
+    const int64_t m = P.m;
+    if (run.fold_mfma) {
+        hipLaunchKernelGGL(k_spx_fold_mask, dim3(run.gM, SPX_DEFER), dim3(SX_WG), 0, run.s, P, cnt); // empty slots: zero columns
+        hipLaunchKernelGGL(k_spx_fold_mfma, dim3(plan::fm_grid(m)), dim3(SX_WG), 0, run.s, P, plan::fm_nkt(m), plan::fm_nic(m));
+        return;
     }
-    if (session && session->valid && vbasis_in && col_ids && static_cast<int64_t>(session->head_ids.size()) == m) {
-        // the session's inverse serves when the warm basis names exactly the variables it belongs to
-        std::vector<int8_t> cb(static_cast<size_t>(m));
-        SX_HIP(hipMemcpyAsync(cb.data(), cbasis_in, static_cast<size_t>(m), hipMemcpyDeviceToHost, s));
-        SX_HIP(hipStreamSynchronize(s));
-        std::unordered_map<int64_t, int32_t> basic_of_id;
-        int64_t n_basic = 0;
-        for (int64_t j = 0; j < n; ++j)
-            if (vb[static_cast<size_t>(j)] == ST_BASIC) {
-                basic_of_id.emplace(col_ids[j], static_cast<int32_t>(j));
-                ++n_basic;
-            }
-        for (int64_t i = 0; i < m; ++i) n_basic += (cb[static_cast<size_t>(i)] == 0) ? 1 : 0;
-        std::vector<int32_t> head_new(static_cast<size_t>(m));
-        bool ok = n_basic == m;
-        for (int64_t i = 0; ok && i < m; ++i) {
-            const int64_t id = session->head_ids[static_cast<size_t>(i)];
-            if (id >= 0) {
-                auto it = basic_of_id.find(id);
-                if (it == basic_of_id.end()) ok = false;
-                else {
-                    head_new[static_cast<size_t>(i)] = it->second;
-                    basic_of_id.erase(it); // every basic column serves one position
-                }
-            } else {
-                const int64_t r = -(id + 1);
-                if (r >= m || cb[static_cast<size_t>(r)] != 0) ok = false;
-                else head_new[static_cast<size_t>(i)] = static_cast<int32_t>(n + r);
-            }
-        }
-        if (ok && basic_of_id.empty()) {
-            int32_t *head_dev = nullptr;
-            SX_TRY(mem.get(static_cast<size_t>(m), &head_dev));
-            SX_HIP(hipMemcpyAsync(head_dev, head_new.data(), sizeof(int32_t) * static_cast<size_t>(m),
-                                  hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_spx_init, dim3(gN), dim3(SX_WG), 0, s, P, l, u, c, 1);
-            hipLaunchKernelGGL(k_spx_apply_vbasis, dim3(grid1d(n)), dim3(SX_WG), 0, s, P, vbasis_in);
-            hipLaunchKernelGGL(k_spx_logicals_out, dim3(gM), dim3(SX_WG), 0, s, P);
-            hipLaunchKernelGGL(k_spx_install_head, dim3(gM), dim3(SX_WG), 0, s, P, head_dev);
-            hipLaunchKernelGGL(k_spx_reset_state, dim3(1), dim3(1), 0, s, P);
-            refresh(true);
-            // the kept inverse is accepted when it still reproduces the constraints: x_B = Binv (b - N x_N) must
-            // satisfy A x + s = b (a basis that is merely infeasible for the new bounds goes through phase 1)
-            double rel = 0.0;
-            SX_TRY(residual(&rel)); // synchronises: head_new may go out of scope afterwards
-            reused = warm = rel <= resid_tol;
+    hipLaunchKernelGGL(k_spx_fold, dim3(plan::fold_grid(m)), dim3(SX_WG), 0, run.s, P, cnt, plan::fold_col_tiles(m));
+}
+
+int spx_measure(SpxRun &run) {
+    hipLaunchKernelGGL(k_spx_measure, dim3(1), dim3(1024), 0, run.s, run.P, run.meas);
+    SX_HIP(hipMemcpyAsync(run.host_meas, run.meas, sizeof(run.host_meas), hipMemcpyDeviceToHost, run.s));
+    SX_HIP(hipStreamSynchronize(run.s));
+    return SX_OK;
+}
+
+// max_i |b_i - (A x)_i - s_i| / (1 + max |b|): what the explicit inverse has drifted by.  Synchronises.
+int spx_residual(const SpxCall &call, const SpxRun &run, double *rel) {
+    const sx_matrix *A = call.A;
+    hipStream_t s = run.s;
+    SX_HIP(hipMemsetAsync(run.resid_dev, 0, 2 * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_spx_residual, dim3(run.gR), dim3(SX_WG), 0, s, run.P, A->csr_tiles, A->n_csr_tiles, A->csr_ptr,
+                       A->csr_idx, A->csr_val, run.resid_dev);
+    unsigned long long h[2] = {0, 0};
+    SX_HIP(hipMemcpyAsync(h, run.resid_dev, sizeof(h), hipMemcpyDeviceToHost, s));
+    SX_HIP(hipStreamSynchronize(s));
+    double worst, bmax;
+    memcpy(&worst, &h[0], sizeof(double));
+    memcpy(&bmax, &h[1], sizeof(double));
+    *rel = worst / (1.0 + bmax);
+    return SX_OK;
+}
+
+// pivot the structural columns flagged basic in vb_host (n codes) into the all-logical basis (identity
+// inverse): for each column the largest available pivot among the rows still held by a logical, rows whose
+// logical the target basis keeps (cb_dev code 0) only as a last resort; a column without a usable row stays
+// non-basic.  s_keep: per row the value its logical keeps when a structural takes the row (nullptr: it goes to 0).
+void spx_install(const SpxCall &call, const SpxRun &run, const std::vector<int8_t> &vb_host, const int8_t *cb_dev,
+                 double *s_keep) {
+    const sx_matrix *A = call.A;
+    const Spx P = keeping(run.P, s_keep);
+    hipStream_t s = run.s;
+    const bool defer = run.defer;
+    int slot = 0;
+    for (int64_t j = 0; j < P.n; ++j) {
+        if (vb_host[static_cast<size_t>(j)] != ST_BASIC) continue;
+        hipLaunchKernelGGL(k_spx_ftran, dim3(run.gM), dim3(SX_WG), 0, s, P, A->csc_ptr, A->csc_idx, A->csc_val,
+                           static_cast<int>(j), 0, defer ? slot : 0, cb_dev);
+        hipLaunchKernelGGL(k_spx_rho, dim3(run.gM), dim3(SX_WG), 0, s, P, static_cast<int>(j), defer ? slot : 0,
+                           defer ? slot : -1);
+        if (!defer) {
+            hipLaunchKernelGGL(k_spx_update_binv, dim3(run.gMM), dim3(SX_WG), 0, s, P);
+        } else if (++slot == SPX_DEFER) {
+            spx_fold(run, P, slot);
+            slot = 0;
         }
     }
-    if (session) session->valid = false; // until this solve has left a basis behind
-    const bool trace = getenv("SX_SPX_TRACE") != nullptr; // stderr: where the wall time of a solve goes
-    auto since_enter = [&]() {
-        (void)hipStreamSynchronize(s);
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
-    };
-    const double t_setup_ms = trace ? since_enter() : 0.0;
-    if (!reused) cold_start(1);
-    double t_crash_ms = 0.0;
-    if (vbasis_in && !reused) {
-        hipLaunchKernelGGL(k_spx_apply_vbasis, dim3(grid1d(n)), dim3(SX_WG), 0, s, P, vbasis_in);
-        if (x_start) {
-            // crossover start: every variable keeps the value of the point -- columns the basis guess wants
-            // basic become superbasic at x_start and are then pivoted in where a row is free, the slack of a
-            // row a structural takes stays at b - A x_start -- so the first basic solution IS the point
-            P.s_keep = s_keep_buf;
-            hipLaunchKernelGGL(k_spx_apply_start, dim3(grid1d(n)), dim3(SX_WG), 0, s, P, vbasis_in, x_start);
-            hipLaunchKernelGGL(k_spx_start_slacks, dim3(gR), dim3(SX_WG), 0, s, P, A->csr_tiles, A->n_csr_tiles,
-                               A->csr_ptr, A->csr_idx, A->csr_val);
-        }
-        install(vb, cbasis_in);
-        P.s_keep = nullptr;
-        if (trace) {
-            const double enq = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
-            fprintf(stderr, "[sx_simplex] warm basis: launches enqueued by %.2f ms\n", enq);
-            t_crash_ms = since_enter();
-        }
-        warm = true; // whatever could be pivoted in stays; infeasibilities go through phase 1
-    }
+    if (defer && slot > 0) spx_fold(run, P, slot);
+    hipLaunchKernelGGL(k_spx_reset_state, dim3(1), dim3(1), 0, s, P);
+}
+
+// rebuild the inverse of the CURRENT basis from its columns (the running inverse has only ever seen
+// rank-one updates and drifts): all logicals back in, identity, the basic structurals pivoted in again
+int spx_reinvert(const SpxCall &call, SpxRun &run) {
+    hipStream_t s = run.s;
+    const int64_t n = run.P.n;
+    hipLaunchKernelGGL(k_spx_export, dim3(run.gN), dim3(SX_WG), 0, s, run.P, static_cast<double *>(nullptr),
+                       static_cast<double *>(nullptr), run.vb_now, run.cb_now);
+    std::vector<int8_t> vb_host(static_cast<size_t>(n));
+    SX_HIP(hipMemcpyAsync(vb_host.data(), run.vb_now, static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+    SX_HIP(hipStreamSynchronize(s));
+    const Spx P = keeping(run.P, run.s_keep_buf); // nothing moves: displaced logicals keep the value they have now
+    hipLaunchKernelGGL(k_spx_logical_basis, dim3(run.gN), dim3(SX_WG), 0, s, P);
+    hipLaunchKernelGGL(k_spx_identity, dim3(run.gMM), dim3(SX_WG), 0, s, P);
+    if (run.defer) SX_HIP(hipMemsetAsync(P.er, 0xff, sizeof(int32_t) * SPX_DEFER, s));
+    spx_install(call, run, vb_host, run.cb_now, run.s_keep_buf);
+    ++run.n_reinvert;
     SX_HIP(hipGetLastError());
-    const double t_start_ms = trace ? since_enter() : 0.0;
+    return SX_OK;
+}
 
-    // ---- phases
-    SpxState host;
-    memset(&host, 0, sizeof(host));
-    const int batch = SPX_DEFER;
-    // pivot number k of a batch; with deferred updates it sees k pending pairs and records its own in slot k
-    auto enqueue_pivot = [&](int k) {
-        if (devex)
+// The warm basis to the host (for this test and for the crash); then: the session's inverse serves when the warm
+// basis names exactly the variables it belongs to (plan::match_kept_head) and still reproduces the constraints.
+// Sets run.reused (and run.warm with it).
+int spx_try_kept_inverse(const SpxCall &call, SpxRun &run) {
+    const sx_simplex_session *session = call.session;
+    hipStream_t s = run.s;
+    const int64_t m = run.P.m, n = run.P.n;
+    if (call.vbasis_in) {
+        run.vb_in.resize(static_cast<size_t>(n));
+        SX_HIP(hipMemcpyAsync(run.vb_in.data(), call.vbasis_in, static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+        SX_HIP(hipStreamSynchronize(s));
+    }
+    if (!(session && session->valid && call.vbasis_in && call.col_ids && static_cast<int64_t>(session->head_ids.size()) == m))
+        return SX_OK;
+    std::vector<int8_t> cb(static_cast<size_t>(m));
+    SX_HIP(hipMemcpyAsync(cb.data(), call.cbasis_in, static_cast<size_t>(m), hipMemcpyDeviceToHost, s));
+    SX_HIP(hipStreamSynchronize(s));
+    std::vector<int32_t> head_new;
+    if (!plan::match_kept_head(session->head_ids, run.vb_in.data(), cb.data(), call.col_ids, n, m, head_new)) return SX_OK;
+    int32_t *head_dev = nullptr;
+    SX_TRY(run.mem.get(static_cast<size_t>(m), &head_dev));
+    SX_HIP(hipMemcpyAsync(head_dev, head_new.data(), sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_spx_init, dim3(run.gN), dim3(SX_WG), 0, s, run.P, call.l, call.u, call.c, 1);
+    hipLaunchKernelGGL(k_spx_apply_vbasis, dim3(grid1d(n)), dim3(SX_WG), 0, s, run.P, call.vbasis_in);
+    hipLaunchKernelGGL(k_spx_logicals_out, dim3(run.gM), dim3(SX_WG), 0, s, run.P);
+    hipLaunchKernelGGL(k_spx_install_head, dim3(run.gM), dim3(SX_WG), 0, s, run.P, head_dev);
+    hipLaunchKernelGGL(k_spx_reset_state, dim3(1), dim3(1), 0, s, run.P);
+    spx_refresh(call, run, true);
+    // the kept inverse is accepted when it still reproduces the constraints: x_B = Binv (b - N x_N) must
+    // satisfy A x + s = b (a basis that is merely infeasible for the new bounds goes through phase 1)
+    double rel = 0.0;
+    SX_TRY(spx_residual(call, run, &rel)); // synchronises: head_new may go out of scope afterwards
+    run.reused = run.warm = rel <= call.feas_tol;
+    return SX_OK;
+}
+
+// without a kept inverse: the all-logical basis, and the structurals of a warm basis pivoted into it (the crash)
+int spx_start_basis(const SpxCall &call, SpxRun &run) {
+    const sx_matrix *A = call.A;
+    hipStream_t s = run.s;
+    const int64_t n = run.P.n;
+    hipLaunchKernelGGL(k_spx_init, dim3(run.gN), dim3(SX_WG), 0, s, run.P, call.l, call.u, call.c, 1);
+    hipLaunchKernelGGL(k_spx_identity, dim3(run.gMM), dim3(SX_WG), 0, s, run.P);
+    if (!call.vbasis_in) return SX_OK;
+    hipLaunchKernelGGL(k_spx_apply_vbasis, dim3(grid1d(n)), dim3(SX_WG), 0, s, run.P, call.vbasis_in);
+    double *s_keep = nullptr;
+    if (call.x_start) {
+        // crossover start: every variable keeps the value of the point -- columns the basis guess wants
+        // basic become superbasic at x_start and are then pivoted in where a row is free, the slack of a
+        // row a structural takes stays at b - A x_start -- so the first basic solution IS the point
+        s_keep = run.s_keep_buf;
+        const Spx P = keeping(run.P, s_keep);
+        hipLaunchKernelGGL(k_spx_apply_start, dim3(grid1d(n)), dim3(SX_WG), 0, s, P, call.vbasis_in, call.x_start);
+        hipLaunchKernelGGL(k_spx_start_slacks, dim3(run.gR), dim3(SX_WG), 0, s, P, A->csr_tiles, A->n_csr_tiles, A->csr_ptr,
+                           A->csr_idx, A->csr_val);
+    }
+    spx_install(call, run, run.vb_in, call.cbasis_in, s_keep);
+    if (run.trace) {
+        fprintf(stderr, "[sx_simplex] warm basis: launches enqueued by %.2f ms\n", spx_ms_since_enter(run, false));
+        run.t_crash_ms = spx_ms_since_enter(run, true);
+    }
+    run.warm = true; // whatever could be pivoted in stays; infeasibilities go through phase 1
+    return SX_OK;
+}
+
+// SPX_DEFER pivots; pivot number k of a batch sees k pending pairs with deferred updates and records its own in slot k
+void spx_enqueue_batch(const SpxCall &call, const SpxRun &run) {
+    const sx_matrix *A = call.A;
+    const Spx &P = run.P;
+    hipStream_t s = run.s;
+    const bool defer = run.defer;
+    const int gP = run.gP, gL = run.gL;
+    for (int k = 0; k < SPX_DEFER; ++k) {
+        if (run.devex)
             hipLaunchKernelGGL(k_spx_price<true>, dim3(gP + gL), dim3(SX_WG), 0, s, P, A->csc_tiles, A->n_csc_tiles,
-                               A->csc_ptr, A->csc_idx, A->csc_val, opt_tol, gP);
+                               A->csc_ptr, A->csc_idx, A->csc_val, call.opt_tol, gP);
         else
             hipLaunchKernelGGL(k_spx_price<false>, dim3(gP + gL), dim3(SX_WG), 0, s, P, A->csc_tiles, A->n_csc_tiles,
-                               A->csc_ptr, A->csc_idx, A->csc_val, opt_tol, gP);
-        hipLaunchKernelGGL(k_spx_ftran, dim3(gM), dim3(SX_WG), 0, s, P, A->csc_ptr, A->csc_idx, A->csc_val, -1, gP + gL,
+                               A->csc_ptr, A->csc_idx, A->csc_val, call.opt_tol, gP);
+        hipLaunchKernelGGL(k_spx_ftran, dim3(run.gM), dim3(SX_WG), 0, s, P, A->csc_ptr, A->csc_idx, A->csc_val, -1, gP + gL,
                            defer ? k : 0, static_cast<const int8_t *>(nullptr));
-        hipLaunchKernelGGL(k_spx_rho_update, dim3(gM), dim3(SX_WG), 0, s, P, defer ? k : 0, defer ? k : -1);
-        if (!defer) hipLaunchKernelGGL(k_spx_update_binv, dim3(gMM), dim3(SX_WG), 0, s, P);
-    };
-    auto enqueue_batch = [&](bool with_fold = true) {
-        for (int k = 0; k < batch; ++k) enqueue_pivot(k);
-        if (defer && with_fold) fold(batch);
-    };
-    // a batch of 64 pivots = 192 small launches (+ the fold) with fixed arguments: captured into a hipGraph and
-    // replayed (pivots are launch-bound for small m); direct launches are the fallback.  Capturing and
-    // instantiating costs milliseconds, more than a short warm-started re-solve takes altogether, so the
-    // graph is only built once a solve has gone through GRAPH_AFTER pivots by direct launches.
-    const int64_t GRAPH_AFTER = 4096; // with 3 launches per pivot replay only insures against a slow host
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool graph_tried = false, graph_has_fold = true;
-    auto build_graph = [&]() {
-        graph_tried = true;
-        if (!ctx->opt_graph) return;
-        // rocprofv3 --kernel-trace (ROCm 7.2) segfaults inside hipGraphLaunch after some thousands of
-        // replays of this graph; with three launches per pivot direct launches are as fast
-        // (profiles/r01/spx_bench.txt), so a profiled run simply does not replay
-        if (getenv("ROCP_TOOL_LIBRARIES") != nullptr) return;
-        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            graph_has_fold = true;
-            enqueue_batch(graph_has_fold);
-            if (hipStreamEndCapture(s, &graph) != hipSuccess || graph == nullptr ||
-                hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess)
-                exec = nullptr;
-        }
-        (void)hipGetLastError();
-    };
-    struct GraphGuard {
-        hipGraph_t &g;
-        hipGraphExec_t &e;
-        ~GraphGuard() {
-            if (e) (void)hipGraphExecDestroy(e);
-            if (g) (void)hipGraphDestroy(g);
-        }
-    } graph_guard{graph, exec};
-
-    // x_B and y from scratch cost two passes over the m x m inverse, a pivot O(m): the interval grows with m
-    // so that the refresh stays a small share of the pivots between two of them (64 up to m = 2048, 2048 from
-    // m = 11.6k on); the residual check every "spx_check" pivots is the safety net either way
-    int64_t refresh_every = 64;
-    {
-        const double scale = static_cast<double>(m) / 2048.0;
-        int64_t want = static_cast<int64_t>(64.0 * scale * scale);
-        want = (want / 64) * 64;
-        refresh_every = want < 64 ? 64 : (want > 2048 ? 2048 : want);
+        hipLaunchKernelGGL(k_spx_rho_update, dim3(run.gM), dim3(SX_WG), 0, s, P, defer ? k : 0, defer ? k : -1);
+        if (!defer) hipLaunchKernelGGL(k_spx_update_binv, dim3(run.gMM), dim3(SX_WG), 0, s, P);
     }
-    int64_t direct_pivots = 0; // over both phases
-    auto run_phase = [&](int64_t budget) -> int {
-        int64_t done_iters = 0;
-        while (true) {
-            if (!exec && !graph_tried && direct_pivots >= GRAPH_AFTER) build_graph();
-            if (!exec) direct_pivots += batch;
-            if (exec) {
-                SX_HIP(hipGraphLaunch(exec, s));
-                if (defer && !graph_has_fold) fold(batch);
-            } else {
-                enqueue_batch();
-            }
-            done_iters += batch;
-            SX_HIP(hipGetLastError());
-            SX_HIP(hipMemcpyAsync(&host, P.st, sizeof(host), hipMemcpyDeviceToHost, s));
-            SX_HIP(hipStreamSynchronize(s));
-            if (host.done || host.iters >= budget) return SX_OK;
-            if (done_iters % refresh_every == 0) refresh(true); // numerical hygiene: x_B and y from scratch
-            if (done_iters % ctx->opt_spx_check == 0) { // and the inverse itself, against the constraints
-                double rel = 0.0;
-                SX_TRY(residual(&rel));
-                if (!(rel <= resid_tol) || ctx->opt_spx_force_reinvert) {
-                    SX_TRY(reinvert());
-                    refresh(true);
-                }
+    if (defer) spx_fold(run, P, SPX_DEFER);
+}
+
+// batches until the phase stops or host.iters reaches the budget; between batches the numerical hygiene
+int spx_run_phase(const SpxCall &call, SpxRun &run, int64_t budget) {
+    sx_ctx *ctx = call.ctx;
+    hipStream_t s = run.s;
+    const int64_t refresh_every = plan::refresh_interval(run.P.m);
+    int64_t done_iters = 0;
+    while (true) {
+        if (!run.graph.ready() && !run.graph_tried && run.direct_pivots >= GRAPH_AFTER) {
+            run.graph_tried = true;
+            if (sx_graph_wanted(ctx, SX_GRAPH_HEED_PROFILER)) {
+                run.graph.capture(s, [&]() { spx_enqueue_batch(call, run); });
+                (void)hipGetLastError();
             }
         }
-    };
+        if (run.graph.ready()) {
+            SX_HIP(run.graph.launch(s));
+        } else {
+            run.direct_pivots += SPX_DEFER;
+            spx_enqueue_batch(call, run);
+        }
+        done_iters += SPX_DEFER;
+        SX_HIP(hipGetLastError());
+        SX_HIP(hipMemcpyAsync(&run.host, run.P.st, sizeof(run.host), hipMemcpyDeviceToHost, s));
+        SX_HIP(hipStreamSynchronize(s));
+        if (run.host.done || run.host.iters >= budget) return SX_OK;
+        if (done_iters % refresh_every == 0) spx_refresh(call, run, true); // x_B and y from scratch
+        if (done_iters % ctx->opt_spx_check == 0) { // and the inverse itself, against the constraints
+            double rel = 0.0;
+            SX_TRY(spx_residual(call, run, &rel));
+            if (!(rel <= call.feas_tol) || ctx->opt_spx_force_reinvert) {
+                SX_TRY(spx_reinvert(call, run));
+                spx_refresh(call, run, true);
+            }
+        }
+    }
+}
 
-    // status codes of sx_simplex_result: 0 optimal, 1 infeasible, 2 unbounded, 3 iteration limit, 4 numerical
-    int status = -1;
-    int64_t phase1_iters = 0;
-    refresh(true);
-    SX_TRY(measure());
-    if (host_meas[0] > feas_tol) {
-        // ---- phase 1: minimise the infeasibility of the relaxed logicals
-        hipLaunchKernelGGL(k_spx_struct_cost, dim3(grid1d(n)), dim3(SX_WG), 0, s, P, 0);
-        hipLaunchKernelGGL(k_spx_reset_state, dim3(1), dim3(1), 0, s, P); // also zeroes the relaxed count
-        hipLaunchKernelGGL(k_spx_phase1_setup, dim3(gM), dim3(SX_WG), 0, s, P, feas_tol);
-        hipLaunchKernelGGL(k_spx_btran, dim3(grid1d(m * 64)), dim3(SX_WG), 0, s, P);
-        SX_TRY(run_phase(max_iter));
-        phase1_iters = host.iters;
-        if (host.done == 3) status = 4;
-        else if (host.done == 0) status = 3;
+// phase 1: minimise the infeasibility of the relaxed logicals; *status stays OPEN when phase 2 may follow
+int spx_phase1(const SpxCall &call, SpxRun &run, int *status) {
+    hipStream_t s = run.s;
+    const int64_t m = run.P.m, n = run.P.n;
+    hipLaunchKernelGGL(k_spx_struct_cost, dim3(grid1d(n)), dim3(SX_WG), 0, s, run.P, 0);
+    hipLaunchKernelGGL(k_spx_reset_state, dim3(1), dim3(1), 0, s, run.P); // also zeroes the relaxed count
+    hipLaunchKernelGGL(k_spx_phase1_setup, dim3(run.gM), dim3(SX_WG), 0, s, run.P, call.feas_tol);
+    hipLaunchKernelGGL(k_spx_btran, dim3(grid1d(m * 64)), dim3(SX_WG), 0, s, run.P);
+    SX_TRY(spx_run_phase(call, run, call.max_iter));
+    run.phase1_iters = run.host.iters;
+    *status = plan::phase1_status(run.host.done);
+    if (*status == plan::OPEN) {
+        spx_refresh(call, run, false);
+        SX_TRY(spx_measure(run));
+        // sum of |relaxed logicals| that are still basic; scaled tolerance on the right-hand side
+        if (run.host_meas[1] > call.feas_tol * (1.0 + static_cast<double>(m)) || run.host_meas[0] > 10 * call.feas_tol)
+            *status = plan::INFEASIBLE;
+    }
+    if (*status == plan::OPEN) {
+        hipLaunchKernelGGL(k_spx_phase2_setup, dim3(run.gN), dim3(SX_WG), 0, s, run.P);
+        hipLaunchKernelGGL(k_spx_reset_state, dim3(1), dim3(1), 0, s, run.P);
+        spx_refresh(call, run, true);
+    }
+    return SX_OK;
+}
+
+// phase 2, and the check the advisor asked for: "optimal" is only reported for a point that satisfies
+// A x + s = b; if the running inverse has drifted, it is rebuilt from the basis columns and the phase
+// resumed from the same basis (twice at most)
+int spx_phase2(const SpxCall &call, SpxRun &run, int *status) {
+    for (int attempt = 0; attempt < 3 && *status == plan::OPEN; ++attempt) {
+        SX_TRY(spx_run_phase(call, run, call.max_iter));
+        *status = plan::phase2_status(run.host.done);
+        if (*status != plan::OPEN) break;
+        spx_refresh(call, run, true);
+        double rel = 0.0;
+        SX_TRY(spx_residual(call, run, &rel));
+        if (rel <= call.feas_tol) *status = plan::OPTIMAL;
+        else if (attempt == 2) *status = plan::NUMERICAL;
         else {
-            refresh(false);
-            SX_TRY(measure());
-            // sum of |relaxed logicals| that are still basic; scaled tolerance on the right-hand side
-            if (host_meas[1] > feas_tol * (1.0 + static_cast<double>(m)) || host_meas[0] > 10 * feas_tol) status = 1;
-        }
-        if (status < 0) {
-            hipLaunchKernelGGL(k_spx_phase2_setup, dim3(gN), dim3(SX_WG), 0, s, P);
-            hipLaunchKernelGGL(k_spx_reset_state, dim3(1), dim3(1), 0, s, P);
-            refresh(true);
+            SX_TRY(spx_reinvert(call, run));
+            spx_refresh(call, run, true);
         }
     }
-    if (status < 0) {
-        // phase 2, and the check the advisor asked for: "optimal" is only reported for a point that satisfies
-        // A x + s = b; if the running inverse has drifted, it is rebuilt from the basis columns and the phase
-        // resumed from the same basis (twice at most)
-        for (int attempt = 0; attempt < 3 && status < 0; ++attempt) {
-            SX_TRY(run_phase(max_iter));
-            if (host.done == 2) status = 2;
-            else if (host.done == 3) status = 4;
-            else if (host.done == 0) status = 3;
-            else {
-                refresh(true);
-                double rel = 0.0;
-                SX_TRY(residual(&rel));
-                if (rel <= resid_tol) status = 0;
-                else if (attempt == 2) status = 4;
-                else {
-                    SX_TRY(reinvert());
-                    refresh(true);
-                }
-            }
-        }
-    }
-    refresh(true);
-    SX_TRY(measure());
-    hipLaunchKernelGGL(k_spx_export, dim3(gN), dim3(SX_WG), 0, s, P, x_out, y_out, vbasis_out, cbasis_out);
+    return SX_OK;
+}
+
+// the point, the duals and the basis to the caller; the result; what the session's inverse now belongs to
+int spx_export_and_remember(const SpxCall &call, SpxRun &run, int status) {
+    sx_simplex_session *session = call.session;
+    const int64_t m = run.P.m, n = run.P.n;
+    spx_refresh(call, run, true);
+    SX_TRY(spx_measure(run));
+    hipLaunchKernelGGL(k_spx_export, dim3(run.gN), dim3(SX_WG), 0, run.s, run.P, call.x_out, call.y_out, call.vbasis_out,
+                       call.cbasis_out);
     SX_HIP(hipGetLastError());
-    SX_HIP(hipStreamSynchronize(s));
-    if (trace) {
-        const double t_all = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
+    SX_HIP(hipStreamSynchronize(run.s));
+    if (run.trace) {
+        const double t_all = spx_ms_since_enter(run, false);
         fprintf(stderr,
                 "[sx_simplex] m=%lld n=%lld start=%s: set-up %.2f ms, basis %.2f ms (columns installed by %.2f), "
                 "phases %.2f ms, %lld pivots (%lld in phase 1), %lld re-inversions, status %d\n",
-                (long long)m, (long long)n, reused ? "kept inverse" : (vbasis_in ? (warm ? "crash" : "crash dropped") : "cold"),
-                t_setup_ms, t_start_ms - t_setup_ms, t_crash_ms > 0 ? t_crash_ms - t_setup_ms : 0.0, t_all - t_start_ms,
-                (long long)host.iters, (long long)phase1_iters, (long long)n_reinvert, status);
+                (long long)m, (long long)n,
+                run.reused ? "kept inverse" : (call.vbasis_in ? (run.warm ? "crash" : "crash dropped") : "cold"),
+                run.t_setup_ms, run.t_start_ms - run.t_setup_ms, run.t_crash_ms > 0 ? run.t_crash_ms - run.t_setup_ms : 0.0,
+                t_all - run.t_start_ms, (long long)run.host.iters, (long long)run.phase1_iters, (long long)run.n_reinvert, status);
     }
+    sx_simplex_result *result = call.result;
     result->status = status;
-    result->iters = host.iters;
-    result->phase1_iters = phase1_iters;
-    result->obj = host_meas[2];
-    result->max_violation = host_meas[0];
-    result->warm_start_used = reused ? 2 : (warm ? 1 : 0);
-    if (session) { // remember which variables the inverse left in P.Binv belongs to
+    result->iters = run.host.iters;
+    result->phase1_iters = run.phase1_iters;
+    result->obj = run.host_meas[2];
+    result->max_violation = run.host_meas[0];
+    result->warm_start_used = run.reused ? 2 : (run.warm ? 1 : 0);
+    if (session) {
         std::vector<int32_t> head_host(static_cast<size_t>(m));
-        SX_HIP(hipMemcpy(head_host.data(), P.head, sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyDeviceToHost));
-        session->head_ids.resize(static_cast<size_t>(m));
-        for (int64_t i = 0; i < m; ++i) {
-            const int32_t k = head_host[static_cast<size_t>(i)];
-            session->head_ids[static_cast<size_t>(i)] = (k < n) ? (col_ids ? col_ids[k] : 0) : -(static_cast<int64_t>(k - n) + 1);
-        }
-        session->valid = col_ids != nullptr && status != 4;
+        SX_HIP(hipMemcpy(head_host.data(), run.P.head, sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyDeviceToHost));
+        plan::head_ids_of(head_host, call.col_ids, n, session->head_ids);
+        session->valid = call.col_ids != nullptr && status != plan::NUMERICAL;
     }
     return SX_OK;
+}
+
+int spx_solve(SpxCall call) {
+    sx_ctx *ctx = call.ctx;
+    sx_simplex_session *session = call.session;
+    const sx_matrix *A = call.A;
+    SX_ENTER(ctx);
+    SX_REQUIRE(session == nullptr || session->ctx == ctx, "the session belongs to another context");
+    SX_REQUIRE(A && call.b && call.c && call.l && call.u && call.row_is_lt && call.result, "NULL argument");
+    SX_REQUIRE(A->csr_ptr && A->csc_ptr, "the simplex needs both layouts of A");
+    SX_REQUIRE((call.vbasis_in == nullptr) == (call.cbasis_in == nullptr), "vbasis_in and cbasis_in go together");
+    memset(call.result, 0, sizeof(*call.result));
+    const int64_t m = A->m, n = A->n;
+    {   // the basis inverse is an explicit dense m x m matrix: it has to fit the HBM that is free now
+        size_t free_b = 0, total_b = 0;
+        SX_HIP(hipMemGetInfo(&free_b, &total_b));
+        const bool have_inverse = session && session->m == m && session->Binv != nullptr;
+        if (!have_inverse && !plan::inverse_fits(m, n + m, free_b)) {
+            sx_set_error("sx_simplex_solve: the dense basis inverse of %lld rows needs %.1f GB, %.1f GB of HBM are free",
+                         (long long)m, plan::inverse_bytes(m, n + m) / 1e9, static_cast<double>(free_b) / 1e9);
+            return SX_ERR_UNSUPPORTED;
+        }
+    }
+    if (call.max_iter <= 0) call.max_iter = plan::default_max_iter(m, n);
+    SpxRun run(ctx);
+    run.t_enter = std::chrono::steady_clock::now();
+    spx_options(call, run);
+    SX_TRY(spx_allocate(call, run));
+
+    SX_TRY(spx_try_kept_inverse(call, run));
+    if (session) session->valid = false; // until this solve has left a basis behind
+    if (run.trace) run.t_setup_ms = spx_ms_since_enter(run, true);
+    if (!run.reused) SX_TRY(spx_start_basis(call, run));
+    SX_HIP(hipGetLastError());
+    if (run.trace) run.t_start_ms = spx_ms_since_enter(run, true);
+
+    int status = plan::OPEN;
+    spx_refresh(call, run, true);
+    SX_TRY(spx_measure(run));
+    if (run.host_meas[0] > call.feas_tol) SX_TRY(spx_phase1(call, run, &status));
+    if (status == plan::OPEN) SX_TRY(spx_phase2(call, run, &status));
+    return spx_export_and_remember(call, run, status);
+}
+
+} // namespace
+
+SX_API int sx_simplex_solve_dev(sx_ctx *ctx, const sx_matrix *A, const double *b, const double *c, const double *l,
+                                const double *u, const uint8_t *row_is_lt, const int8_t *vbasis_in,
+                                const int8_t *cbasis_in, int64_t max_iter, double feas_tol, double opt_tol,
+                                double *x_out, double *y_out, int8_t *vbasis_out, int8_t *cbasis_out,
+                                sx_simplex_result *result) {
+    return spx_solve(SpxCall{ctx, nullptr, A, b, c, l, u, row_is_lt, vbasis_in, cbasis_in, /*col_ids*/ nullptr,
+                             /*x_start*/ nullptr, max_iter, feas_tol, opt_tol, x_out, y_out, vbasis_out, cbasis_out, result});
+}
+
+SX_API int sx_simplex_solve_session_dev(sx_ctx *ctx, sx_simplex_session *session, const sx_matrix *A, const double *b,
+                                        const double *c, const double *l, const double *u, const uint8_t *row_is_lt,
+                                        const int8_t *vbasis_in, const int8_t *cbasis_in, const int64_t *col_ids,
+                                        int64_t max_iter, double feas_tol, double opt_tol, double *x_out,
+                                        double *y_out, int8_t *vbasis_out, int8_t *cbasis_out,
+                                        sx_simplex_result *result) {
+    return spx_solve(SpxCall{ctx, session, A, b, c, l, u, row_is_lt, vbasis_in, cbasis_in, col_ids, /*x_start*/ nullptr,
+                             max_iter, feas_tol, opt_tol, x_out, y_out, vbasis_out, cbasis_out, result});
+}
+
+SX_API int sx_simplex_crossover_dev(sx_ctx *ctx, const sx_matrix *A, const double *b, const double *c, const double *l,
+                                    const double *u, const uint8_t *row_is_lt, const int8_t *vbasis_in,
+                                    const int8_t *cbasis_in, const double *x_start, int64_t max_iter, double feas_tol,
+                                    double opt_tol, double *x_out, double *y_out, int8_t *vbasis_out,
+                                    int8_t *cbasis_out, sx_simplex_result *result) {
+    SX_REQUIRE(x_start != nullptr && vbasis_in != nullptr && cbasis_in != nullptr,
+               "sx_simplex_crossover_dev needs a starting point and a basis guess");
+    return spx_solve(SpxCall{ctx, nullptr, A, b, c, l, u, row_is_lt, vbasis_in, cbasis_in, /*col_ids*/ nullptr, x_start,
+                             max_iter, feas_tol, opt_tol, x_out, y_out, vbasis_out, cbasis_out, result});
 }

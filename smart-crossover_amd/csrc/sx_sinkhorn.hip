@@ -13,6 +13,7 @@
 // (no MFMA: a single right-hand side is a GEMV) replayed as a hipGraph of 10 iterations.  K^T u uses
 // lanes along the columns with the rows cut into slices (coalesced, no atomics, fixed summation order);
 // K v uses one wave per row.
+#include "sx_graph.h"
 #include "sx_internal.h"
 #include "sx_segwalk.h"
 
@@ -211,22 +212,19 @@ SX_API int sx_sinkhorn_dev(sx_ctx *ctx, int64_t S, int64_t D, const double *a, c
     };
     // iterations come in groups of ten, the first of each group carrying the stopping test (ii % 10 == 0);
     // a group is captured once into a hipGraph and replayed, the host reads the state between groups
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (ctx->opt_graph && max_iter >= 20 && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        for (int k = 0; k < 10; ++k) iteration(k == 0);
-        if (hipStreamEndCapture(s, &graph) != hipSuccess || graph == nullptr ||
-            hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess)
-            exec = nullptr;
-    }
+    SxGraphBatch graph;
+    if (max_iter >= 20 && sx_graph_wanted(ctx, 0))
+        graph.capture(s, [&]() {
+            for (int k = 0; k < 10; ++k) iteration(k == 0);
+        });
     (void)hipGetLastError();
     SkState host;
     memset(&host, 0, sizeof(host));
     int rc = SX_OK;
     int64_t launched = 0;
     while (launched < max_iter && !host.done) {
-        if (exec && launched + 10 <= max_iter) {
-            if (hipGraphLaunch(exec, s) != hipSuccess) rc = SX_ERR_HIP;
+        if (graph.ready() && launched + 10 <= max_iter) {
+            if (graph.launch(s) != hipSuccess) rc = SX_ERR_HIP;
             launched += 10;
         } else {
             const int64_t upto = (launched + 10 < max_iter) ? launched + 10 : max_iter;
@@ -236,13 +234,9 @@ SX_API int sx_sinkhorn_dev(sx_ctx *ctx, int64_t S, int64_t D, const double *a, c
             hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess) {
             sx_set_error("Sinkhorn iteration batch failed");
-            rc = SX_ERR_HIP;
-            break;
+            return SX_ERR_HIP;
         }
     }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (rc != SX_OK) return rc;
     if (plan) hipLaunchKernelGGL(k_sk_plan, dim3(grid1d(S * D)), dim3(SX_WG), 0, s, S, D, K, u, v, plan);
     if (u_out) SX_HIP(hipMemcpyAsync(u_out, u, sizeof(double) * uS, hipMemcpyDeviceToDevice, s));
     if (v_out) SX_HIP(hipMemcpyAsync(v_out, v, sizeof(double) * uD, hipMemcpyDeviceToDevice, s));

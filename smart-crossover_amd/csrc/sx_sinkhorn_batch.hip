@@ -15,6 +15,7 @@
 // operand of a k-step (4 rows x 16 instances) is 512 contiguous bytes; K and K^T both resident (4.9 MB each
 // at 784 x 784) so that the A operand of either product is read along rows.  One workgroup per 16 output
 // rows; its four waves split the contraction and their tiles are added in wave order (fixed order).
+#include "sx_graph.h"
 #include "sx_internal.h"
 #include "sx_segwalk.h"
 
@@ -285,22 +286,19 @@ SX_API int sx_sinkhorn_batch_dev(sx_ctx *ctx, int64_t S, int64_t D, int64_t B, c
             hipLaunchKernelGGL(k_skb_count, dim3(1), dim3(64), 0, s, st, err_part, static_cast<int>(tD), stop_thr);
         }
     };
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (ctx->opt_graph && max_iter >= 20 && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        for (int k = 0; k < 10; ++k) iteration(k == 0);
-        if (hipStreamEndCapture(s, &graph) != hipSuccess || graph == nullptr ||
-            hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess)
-            exec = nullptr;
-    }
+    SxGraphBatch graph;
+    if (max_iter >= 20 && sx_graph_wanted(ctx, 0))
+        graph.capture(s, [&]() {
+            for (int k = 0; k < 10; ++k) iteration(k == 0);
+        });
     (void)hipGetLastError();
     SkbState host;
     memset(&host, 0, sizeof(host));
     int rc = SX_OK;
     int64_t launched = 0;
     while (launched < max_iter && !host.all_done) {
-        if (exec && launched + 10 <= max_iter) {
-            if (hipGraphLaunch(exec, s) != hipSuccess) rc = SX_ERR_HIP;
+        if (graph.ready() && launched + 10 <= max_iter) {
+            if (graph.launch(s) != hipSuccess) rc = SX_ERR_HIP;
             launched += 10;
         } else {
             const int64_t upto = (launched + 10 < max_iter) ? launched + 10 : max_iter;
@@ -310,13 +308,9 @@ SX_API int sx_sinkhorn_batch_dev(sx_ctx *ctx, int64_t S, int64_t D, int64_t B, c
             hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess) {
             sx_set_error("batched Sinkhorn iteration group failed");
-            rc = SX_ERR_HIP;
-            break;
+            return SX_ERR_HIP;
         }
     }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (rc != SX_OK) return rc;
     if (plans) hipLaunchKernelGGL(k_skb_plan, dim3(grid1d(S * D)), dim3(SX_WG), 0, s, S, D, static_cast<int>(B), K, U, V, plans);
     if (u_out) hipLaunchKernelGGL(k_skb_unpack, dim3(grid1d(S * B, 1 << 20)), dim3(SX_WG), 0, s, S, static_cast<int>(B), U, u_out);
     if (v_out) hipLaunchKernelGGL(k_skb_unpack, dim3(grid1d(D * B, 1 << 20)), dim3(SX_WG), 0, s, D, static_cast<int>(B), V, v_out);

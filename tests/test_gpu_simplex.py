@@ -357,6 +357,48 @@ def test_perturbation_crossover_re_solves_on_the_device():
         check_vertex(lp, out, ref.obj_val)
 
 
+def test_graph_replay_equals_direct_launches():
+    """The batch graph is only built after 4,096 pivots by direct launches (GRAPH_AFTER), so a solve has to pass that
+    mark for the replay to run at all: the cold solve of test_cold_start_matches_highs' 400 x 1600 LP takes 10,356 pivots
+    (1,779 of them in phase 1).  Option "graph" 0 and 1 launch the same kernels in the same order: same certificates,
+    same counts, and the same bits in x, y and the basis."""
+    from types import SimpleNamespace
+
+    from smart_crossover.hip import Context
+    from smart_crossover.output import Basis
+    from smart_crossover.solver_caller.solving import solve_lp
+    inst = workloads.sparse_lp(400, 1600, 5, seed=77, stratified=False, frac_upper=0.4)
+    lp = general_lp(inst)
+    ref = solve_lp(lp, "HGS", "default", settings())
+    assert ref.status == "OPTIMAL"
+    m, n = inst.A.shape
+    ctx = Context(0)
+    dA = ctx.matrix(inst.A)
+    put = lambda v: ctx.to_device(np.ascontiguousarray(v, dtype=np.float64))   # noqa: E731
+    d_b, d_c, d_l, d_u = put(inst.b), put(inst.c), put(inst.l), put(inst.u)
+    d_lt = ctx.to_device((np.asarray(inst.sense) == "<").astype(np.uint8))
+    got = {}
+    for graph in (0, 1):
+        ctx.set_option("graph", graph)
+        x, y = ctx.empty(n, np.float64), ctx.empty(m, np.float64)
+        vb, cb = ctx.empty(n, np.int8), ctx.empty(m, np.int8)
+        res = ctx.simplex(dA, d_b, d_c, d_l, d_u, d_lt, None, None, 0, 1e-7, 1e-7, x, y, vb, cb)
+        got[graph] = SimpleNamespace(res=res, x=x.download(), y=y.download(), vb=vb.download(), cb=cb.download())
+    dA.free()
+    ctx.close()
+    for g in got.values():
+        assert int(g.res.status) == 0
+        check_vertex(lp, SimpleNamespace(status="OPTIMAL", obj_val=float(g.res.obj), x=g.x, y=g.y,
+                                         basis=Basis(g.vb.astype(int), g.cb.astype(int))), ref.obj_val)
+    direct, replay = got[0], got[1]
+    assert int(replay.res.iters) >= 4096 + 128                     # (no replay below that: the test would compare nothing)
+    for field in ("status", "iters", "phase1_iters"):
+        assert int(getattr(direct.res, field)) == int(getattr(replay.res, field)), field
+    assert np.array_equal(direct.x.view(np.uint64), replay.x.view(np.uint64))
+    assert np.array_equal(direct.y.view(np.uint64), replay.y.view(np.uint64))
+    assert np.array_equal(direct.vb, replay.vb) and np.array_equal(direct.cb, replay.cb)
+
+
 @pytest.mark.parametrize("m,n,k,seed", [(37, 90, 3, 1), (300, 900, 4, 2), (1000, 2500, 5, 3)])
 def test_matrix_core_fold_agrees_with_the_scalar_fold(monkeypatch, m, n, k, seed):
     """The rank-64 update of the dense inverse on the fp64 matrix cores (k_spx_fold_mfma; by default from 8192 rows
