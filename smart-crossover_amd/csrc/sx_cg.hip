@@ -12,6 +12,7 @@
 // Reductions are two-stage with a fixed order: results are reproducible run to run.  The recurrence
 // and the stopping rule (||r|| < tol*||b||, tested before each iteration; legacy immediate exit when
 // ||b|| <= tol) are those of the reference's pinned scipy.
+#include "sx_cg_plan.h"
 #include "sx_graph.h"
 #include "sx_internal.h"
 #include "sx_rowblock.h"
@@ -22,8 +23,10 @@
 
 namespace {
 
-constexpr int CG_CHUNK = 4096;
-constexpr int CG_GRID = 2048; // workgroups of the grid-stride SpMV passes = number of partials
+namespace plan = sx_cg_plan;
+constexpr int CG_CHUNK = 4096;       // entries per LDS chunk of the plain walks
+constexpr int CG_GRID = plan::GRID;  // workgroups of the grid-stride SpMV passes = number of partials
+static_assert(SX_WG == plan::WG, "the plan's grids assume the walks' workgroup");
 
 struct CgState {
     double rho[2];     // r.r of the current / next iteration (indexed by iteration parity)
@@ -315,12 +318,6 @@ void launch_cg_at(hipStream_t s, const CgState *st, const sx_matrix *A, int gT, 
                            A->csc_idx, A->csc_val, in, scale, out);
 }
 
-inline int grid_for(const sx_ctx *ctx, int64_t ntiles) {
-    int64_t g = ntiles < CG_GRID ? ntiles : CG_GRID;
-    if (ctx->opt_xcd_swizzle && ntiles >= 64) g &= ~static_cast<int64_t>(7);
-    return static_cast<int>(g < 1 ? 1 : g);
-}
-
 // degenerate shapes: with no rows Y is empty and the projector is the identity, proj = xa .* c; with no
 // columns the only directions are slack columns, which Y = diag(xs) pins to zero wherever xs != 0
 __global__ __launch_bounds__(1024) void k_cg_no_rows(int64_t n, const double *__restrict__ xa,
@@ -342,6 +339,137 @@ __global__ __launch_bounds__(1024) void k_cg_no_rows(int64_t n, const double *__
         for (int w = 1; w < 16; ++w) t += part[w];
         *sumsq_out = t;
     }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Host side.  The three drivers of this file -- single device, sharded over ranks, inner CG of the free branch -- are
+// the stages below over a CgPlan (how the two passes over A are launched) and a CgBufs (where the vectors live); the
+// arithmetic of both is sx_cg_plan.h's.  What differs between the drivers stands in the drivers.
+
+struct CgPlan {
+    const sx_matrix *A = nullptr;
+    int gT = 1, gA = 1, gv = 1;      // workgroups of the column pass, of the plain row pass, of the vector kernels
+    int swzT = 0, swzA = 0;          // XCD-contiguous tile map of the column / row pass
+    int win_run = 0;                 // column pass behind the LDS operand window: tiles per load (0: plain walk)
+    const sx_rowblock *rb = nullptr; // row pass over the column-blocked copy of the rows (nullptr: plain walk)
+    int nA = 1;                      // partials the last row pass left in ppq
+};
+
+// vec_len: the longest vector of the vector kernels.  plain: the plain walks, and nothing is built for A -- the free
+// branch's gathered block lives for one call.  Otherwise the window table and the row-block copy are built here on
+// their first use, outside any graph capture; ws_bytes > 0 grows ctx->ws between the two, where the single-device
+// driver always has.
+int cg_plan(sx_ctx *ctx, const sx_matrix *A, int64_t vec_len, bool plain, size_t ws_bytes, CgPlan *pl) {
+    pl->A = A;
+    pl->swzT = sx_csc_swizzle(ctx, A);
+    pl->swzA = sx_csr_swizzle(ctx, A);
+    pl->gT = plan::walk_grid(A->n_csc_tiles, ctx->opt_xcd_swizzle != 0);
+    pl->gA = pl->nA = plan::walk_grid(A->n_csr_tiles, ctx->opt_xcd_swizzle != 0);
+    pl->gv = plan::vector_grid(vec_len);
+    if (plain) return SX_OK;
+    SX_TRY(sx_window_run_csc(ctx, A, &pl->win_run));
+    if (ws_bytes) SX_TRY(sx_reserve(ctx, ws_bytes));
+    return sx_rowblock_get(ctx, A, &pl->rb);
+}
+
+struct CgBufs {
+    CgState *st = nullptr;
+    double *ppq = nullptr, *prr = nullptr; // partials of p.q (or q.q) from the row pass, of r.r from the update
+    double *z = nullptr, *r = nullptr, *p = nullptr, *q = nullptr; // [len]
+    double *w = nullptr, *atz = nullptr;   // results of the column pass
+    int64_t len = 0;
+};
+
+CgBufs cg_carve(void *base, int64_t m, int64_t n) {
+    const plan::Layout L = plan::layout(m, n);
+    char *at = static_cast<char *>(base);
+    auto vec = [at](size_t off) { return reinterpret_cast<double *>(at + off); };
+    CgBufs b;
+    b.st = reinterpret_cast<CgState *>(at + L.state);
+    b.ppq = vec(L.ppq), b.prr = vec(L.prr);
+    b.z = vec(L.z), b.r = vec(L.r), b.p = vec(L.p), b.q = vec(L.q);
+    b.w = vec(L.w), b.atz = vec(L.atz);
+    b.len = m;
+    return b;
+}
+
+// column pass: out = scale^2 .* (A^T in)
+void cg_cols(sx_ctx *ctx, const CgPlan &pl, const CgBufs &b, const double *in, const double *scale, double *out) {
+    launch_cg_at(ctx->stream, b.st, pl.A, pl.gT, pl.swzT, pl.win_run, in, scale, out);
+}
+
+// row pass: out = A vec, partials of out.out in ppq; with pvec the slack term is fused in, out = A vec + xs^2 .* pvec,
+// partials of pvec.out.  pl.nA = number of partials either walk leaves
+int cg_rows(sx_ctx *ctx, CgPlan &pl, const CgBufs &b, const double *vec, const double *xs, const double *pvec, double *out) {
+    const sx_matrix *A = pl.A;
+    if (pl.rb) return sx_rb_cg_a(ctx, pl.rb, A->n, b.st, vec, xs, pvec, out, b.ppq, CG_GRID, &pl.nA);
+    hipLaunchKernelGGL(k_cg_a, dim3(pl.gA), dim3(SX_WG), 0, ctx->stream, b.st, A->csr_tiles, A->n_csr_tiles, pl.swzA,
+                       A->csr_ptr, A->csr_idx, A->csr_val, vec, xs, pvec, out, b.ppq);
+    pl.nA = pl.gA;
+    return SX_OK;
+}
+
+// this device's share of b = Y v: out = A (xa^2 .* c)
+int cg_rhs(sx_ctx *ctx, CgPlan &pl, const CgBufs &b, const double *xa, const double *xs, const double *c, double *out) {
+    hipLaunchKernelGGL(k_cg_scale_c, dim3(pl.gv), dim3(SX_WG), 0, ctx->stream, pl.A->n, xa, c, b.w);
+    return cg_rows(ctx, pl, b, b.w, xs, nullptr, out);
+}
+
+int cg_poll(sx_ctx *ctx, const CgBufs &b, CgState *host) {
+    SX_HIP(hipMemcpyAsync(host, b.st, sizeof(*host), hipMemcpyDeviceToHost, ctx->stream));
+    SX_HIP(hipStreamSynchronize(ctx->stream));
+    return SX_OK;
+}
+
+void cg_arm(sx_ctx *ctx, const CgBufs &b, double atol, int done) {
+    hipLaunchKernelGGL(k_cg_set_atol, dim3(1), dim3(1), 0, ctx->stream, b.st, atol, done);
+}
+
+// begin, with b in r and the n_rho0 partials of b.b in ppq: z = 0, p = r, rho0; ||b|| comes to the host, which decides
+// by `rule` (sx_cg_plan.h) and arms the kernels with atol = tol ||b||
+int cg_begin(sx_ctx *ctx, const CgPlan &pl, const CgBufs &b, int n_rho0, double tol, plan::Start (*rule)(double, double),
+             double *bnrm, plan::Start *start) {
+    hipLaunchKernelGGL(k_cg_init, dim3(pl.gv), dim3(SX_WG), 0, ctx->stream, b.st, b.len, b.ppq, n_rho0, b.r, b.p, b.z);
+    CgState host;
+    SX_TRY(cg_poll(ctx, b, &host));
+    *bnrm = sqrt(host.rho[0]);
+    *start = rule(*bnrm, tol);
+    cg_arm(ctx, b, tol * *bnrm, start->done);
+    return SX_OK;
+}
+
+// update, with q complete and the n_pq partials of p.q in ppq: alpha, z, r (n_rr partials of r.r in prr), stop test, beta, p
+void cg_update(sx_ctx *ctx, const CgPlan &pl, const CgBufs &b, int parity, int n_pq, int n_rr) {
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(k_cg_update_zr, dim3(pl.gv), dim3(SX_WG), 0, s, b.st, parity, b.len, b.ppq, n_pq, b.p, b.q, b.z, b.r, b.prr);
+    hipLaunchKernelGGL(k_cg_update_p, dim3(pl.gv), dim3(SX_WG), 0, s, b.st, parity, b.len, b.prr, n_rr, b.r, b.p);
+}
+
+// projection: columns xa .* (c - A^T z), gv partials of their squares in ppq; slack rows xs .* (cs - z), gv partials in
+// prr.  A^T z is taken with unit scale (dividing xa^2 (A^T z) by xa would break on xa = 0), so w becomes a vector of
+// ones first.  An empty column block (sharded only) leaves zeros in ppq.
+int cg_project(sx_ctx *ctx, const CgPlan &pl, const CgBufs &b, const double *xa, const double *xs, const double *c,
+               const double *cs, double atol, double *proj_cols, double *proj_rows) {
+    hipStream_t s = ctx->stream;
+    const int64_t n = pl.A->n;
+    cg_arm(ctx, b, atol, 0); // re-arm the kernels
+    if (n > 0) {
+        hipLaunchKernelGGL(k_cg_ones, dim3(pl.gv), dim3(SX_WG), 0, s, n, b.w);
+        cg_cols(ctx, pl, b, b.z, b.w, b.atz);
+        hipLaunchKernelGGL(k_cg_proj_cols, dim3(pl.gv), dim3(SX_WG), 0, s, n, xa, c, b.atz, b.ppq, proj_cols);
+    } else {
+        SX_HIP(hipMemsetAsync(b.ppq, 0, sizeof(double) * pl.gv, s));
+    }
+    hipLaunchKernelGGL(k_cg_proj_rows, dim3(pl.gv), dim3(SX_WG), 0, s, b.len, xs, cs, b.z, b.prr, proj_rows);
+    return SX_OK;
+}
+
+// what the loop left, from the state as downloaded after it (proj_norm is the caller's)
+void cg_result(const CgState &host, double bnrm, bool trivial, sx_cg_result *result) {
+    result->b_norm = bnrm;
+    result->iters = host.iters;
+    result->converged = plan::converged(trivial, host.converged);
+    result->rel_residual = plan::rel_residual(host.rho, host.iters, bnrm);
 }
 
 } // namespace
@@ -379,74 +507,35 @@ SX_API int sx_projector_std_dev(sx_ctx *ctx, const sx_matrix *A, const double *x
         return SX_OK;
     }
 
-    const int swzT = sx_csc_swizzle(ctx, A);
-    const int swzA = (ctx->opt_xcd_swizzle && A->n_csr_tiles >= 64 && A->csr_imbalance <= SX_SWIZZLE_MAX_IMBALANCE) ? 1 : 0;
-    const int gT = grid_for(ctx, A->n_csc_tiles), gA = grid_for(ctx, A->n_csr_tiles);
-    // vector kernels: grid-stride with ~4 elements per lane, at most 1024 workgroups (= partials); a
-    // grid sized for the larger of m and n keeps small problems from launching mostly idle blocks
-    int64_t gv64 = ((m > n ? m : n) + 4 * SX_WG - 1) / (4 * SX_WG);
-    const int gv = static_cast<int>(gv64 < 1 ? 1 : (gv64 > 1024 ? 1024 : gv64));
-
-    // column pass behind the LDS operand window when the matrix's auto rule (or the option) says so; the
-    // table is built here, outside any graph capture
-    int win_run = 0;
-    SX_TRY(sx_window_run_csc(ctx, A, &win_run));
-    // workspace: state | partial_pq[CG_GRID] | partial_rr[CG_GRID] | z r p q [m] | w atz [n]
-    const size_t off_state = 0;
-    const size_t off_ppq = 256;
-    const size_t off_prr = off_ppq + sizeof(double) * CG_GRID;
-    const size_t off_vec = off_prr + sizeof(double) * CG_GRID;
-    const size_t bytes =
-        off_vec + sizeof(double) * (4 * static_cast<size_t>(m) + 2 * static_cast<size_t>(n)) + 256;
-    SX_TRY(sx_reserve(ctx, bytes));
-    char *base = static_cast<char *>(ctx->ws);
-    CgState *st = reinterpret_cast<CgState *>(base + off_state);
-    double *ppq = reinterpret_cast<double *>(base + off_ppq);
-    double *prr = reinterpret_cast<double *>(base + off_prr);
-    double *z = reinterpret_cast<double *>(base + off_vec);
-    double *r = z + m, *p = r + m, *q = p + m, *w = q + m, *atz = w + n;
+    // ---- plan: launch geometry, window table and row-block copy; the vectors in ctx->ws
+    CgPlan pl;
+    SX_TRY(cg_plan(ctx, A, m > n ? m : n, false, plan::layout(m, n).bytes, &pl));
+    const CgBufs b = cg_carve(ctx->ws, m, n);
     hipStream_t s = ctx->stream;
 
-    auto launch_at = [&](const double *in, const double *scale, double *out) {
-        launch_cg_at(s, st, A, gT, swzT, win_run, in, scale, out);
-    };
-    // row pass q = A w (+ xs^2 .* p), partials of p.q (or q.q) in ppq: over the column-blocked copy of the rows
-    // when the matrix has one (sx_rowblock.h), else the plain walk; nA = number of partials either leaves
-    const sx_rowblock *rb = nullptr;
-    SX_TRY(sx_rowblock_get(ctx, A, &rb));
-    int nA = gA;
-    auto launch_a = [&](const double *vec, const double *pvec, double *out) -> int {
-        if (rb) return sx_rb_cg_a(ctx, rb, n, st, vec, xs, pvec, out, ppq, CG_GRID, &nA);
-        hipLaunchKernelGGL(k_cg_a, dim3(gA), dim3(SX_WG), 0, s, st, A->csr_tiles, A->n_csr_tiles, swzA, A->csr_ptr,
-                           A->csr_idx, A->csr_val, vec, xs, pvec, out, ppq);
-        return SX_OK;
-    };
-    SX_HIP(hipMemsetAsync(st, 0, sizeof(CgState), s));
-    // b = A (xa^2 .* c) -> r ; rho0 = b.b
-    hipLaunchKernelGGL(k_cg_scale_c, dim3(gv), dim3(SX_WG), 0, s, n, xa, c, w);
-    SX_TRY(launch_a(w, nullptr, r));
-    int n_rho0 = nA;
+    // ---- right-hand side b = A (xa^2 .* c) -> r, partials of b.b from the row pass
+    SX_HIP(hipMemsetAsync(b.st, 0, sizeof(CgState), s));
+    SX_TRY(cg_rhs(ctx, pl, b, xa, xs, c, b.r));
+    int n_rho0 = pl.nA;
     if (cs) { // slack columns carry a cost: b += xs^2 .* cs, rho0 recomputed from the completed b
-        hipLaunchKernelGGL(k_cg_slack_cost, dim3(gv), dim3(SX_WG), 0, s, m, xs, cs, r, ppq);
-        n_rho0 = gv;
+        hipLaunchKernelGGL(k_cg_slack_cost, dim3(pl.gv), dim3(SX_WG), 0, s, m, xs, cs, b.r, b.ppq);
+        n_rho0 = pl.gv;
     }
-    hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(SX_WG), 0, s, st, m, ppq, n_rho0, r, p, z);
-    CgState host;
-    SX_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-    SX_HIP(hipStreamSynchronize(s));
-    const double bnrm = sqrt(host.rho[0]);
-    result->b_norm = bnrm;
-    const bool trivial = !(bnrm > tol); // legacy scipy: ||b|| <= tol -> return x0 = 0 at once
-    hipLaunchKernelGGL(k_cg_set_atol, dim3(1), dim3(1), 0, s, st, tol * bnrm, trivial ? 1 : 0);
 
+    // ---- begin
+    double bnrm = 0.0;
+    plan::Start start;
+    SX_TRY(cg_begin(ctx, pl, b, n_rho0, tol, plan::start_single, &bnrm, &start));
+
+    // ---- loop
+    CgState host;
     int launched = 0;
-    bool finished = trivial;
-    if (!trivial && !(bnrm < tol * bnrm)) { // scipy tests ||r|| < atol before the first iteration too
+    bool finished = start.trivial;
+    if (start.run) {
         auto enqueue_iteration = [&](int par) {
-            launch_at(p, xa, w);
-            (void)launch_a(w, p, q);
-            hipLaunchKernelGGL(k_cg_update_zr, dim3(gv), dim3(SX_WG), 0, s, st, par, m, ppq, nA, p, q, z, r, prr);
-            hipLaunchKernelGGL(k_cg_update_p, dim3(gv), dim3(SX_WG), 0, s, st, par, m, prr, gv, r, p);
+            cg_cols(ctx, pl, b, b.p, xa, b.w);
+            (void)cg_rows(ctx, pl, b, b.w, xs, b.p, b.q); // no early return from inside a stream capture; the poll reports
+            cg_update(ctx, pl, b, par, pl.nA, pl.gv);
         };
         // the loop is launch-bound on cache-resident problems (four ~4 us kernels per iteration): a
         // batch of 24 iterations (even, so the rho parity repeats) is captured once into a hipGraph and
@@ -471,32 +560,21 @@ SX_API int sx_projector_std_dev(sx_ctx *ctx, const sx_matrix *A, const double *x
                 const int upto = (launched + batch < maxiter) ? launched + batch : maxiter;
                 for (; launched < upto; ++launched) enqueue_iteration(launched & 1);
             }
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess) {
+            if (hipGetLastError() != hipSuccess || cg_poll(ctx, b, &host) != SX_OK) {
                 sx_set_error("CG iteration batch failed");
                 return SX_ERR_HIP;
             }
             finished = host.done != 0;
         }
     }
-    SX_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-    SX_HIP(hipStreamSynchronize(s));
-    result->iters = host.iters;
-    result->converged = trivial ? 1 : host.converged;
-    result->rel_residual = bnrm > 0 ? sqrt(host.rho[host.iters & 1]) / bnrm : 0.0;
+    SX_TRY(cg_poll(ctx, b, &host));
+    cg_result(host, bnrm, start.trivial, result);
 
-    // ||proj||: columns xa .* (c - A^T z), slack rows -xs .* z.  A^T z is taken with unit scale
-    // (dividing xa^2 (A^T z) by xa would break on xa = 0), so w becomes a vector of ones first.
-    hipLaunchKernelGGL(k_cg_set_atol, dim3(1), dim3(1), 0, s, st, tol * bnrm, 0); // re-arm the kernels
-    hipLaunchKernelGGL(k_cg_ones, dim3(gv), dim3(SX_WG), 0, s, n, w);
-    launch_at(z, w, atz);
-    hipLaunchKernelGGL(k_cg_proj_cols, dim3(gv), dim3(SX_WG), 0, s, n, xa, c, atz, ppq, proj_cols);
-    hipLaunchKernelGGL(k_cg_proj_rows, dim3(gv), dim3(SX_WG), 0, s, m, xs, cs, z, prr, proj_rows);
-    hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(SX_WG), 0, s, st, ppq, gv, prr, gv);
+    // ---- projection and its norm: columns and slack rows in one sum
+    SX_TRY(cg_project(ctx, pl, b, xa, xs, c, cs, tol * bnrm, proj_cols, proj_rows));
+    hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(SX_WG), 0, s, b.st, b.ppq, pl.gv, b.prr, pl.gv);
     SX_HIP(hipGetLastError());
-    SX_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-    SX_HIP(hipStreamSynchronize(s));
+    SX_TRY(cg_poll(ctx, b, &host));
     result->proj_norm = sqrt(host.sumsq);
     return SX_OK;
 }
@@ -564,33 +642,12 @@ __global__ __launch_bounds__(SX_WG) void k_cg_take_rhs(int64_t m, const double *
 
 struct sx_cg_shard {
     sx_ctx *ctx = nullptr;
-    const sx_matrix *A = nullptr;
-    const double *xa = nullptr, *xs = nullptr, *c = nullptr, *cs = nullptr;
+    const double *xa = nullptr, *xs = nullptr, *c = nullptr, *cs = nullptr; // the caller's, alive until close
     double tol = 0.0, bnrm = 0.0;
-    int64_t m = 0, n = 0;
-    char *block = nullptr; // one allocation: state | partials | z r p q | w atz
-    CgState *st = nullptr;
-    double *ppq = nullptr, *prr = nullptr, *z = nullptr, *r = nullptr, *p = nullptr, *q = nullptr, *w = nullptr, *atz = nullptr;
-    int gT = 1, gA = 1, gv = 1, swzT = 0, swzA = 0, win_run = 0, nA = 1;
-    const sx_rowblock *rb = nullptr;
+    char *block = nullptr; // one allocation, carved into b
+    CgPlan pl;
+    CgBufs b;
 };
-
-namespace {
-
-void shard_at(sx_cg_shard *h, const double *in, const double *scale, double *out) {
-    launch_cg_at(h->ctx->stream, h->st, h->A, h->gT, h->swzT, h->win_run, in, scale, out);
-}
-
-int shard_a(sx_cg_shard *h, const double *vec, double *out) { // out = A_loc vec, partials of out.out in ppq
-    const sx_matrix *A = h->A;
-    if (h->rb) return sx_rb_cg_a(h->ctx, h->rb, h->n, h->st, vec, h->xs, nullptr, out, h->ppq, CG_GRID, &h->nA);
-    hipLaunchKernelGGL(k_cg_a, dim3(h->gA), dim3(SX_WG), 0, h->ctx->stream, h->st, A->csr_tiles, A->n_csr_tiles, h->swzA,
-                       A->csr_ptr, A->csr_idx, A->csr_val, vec, h->xs, static_cast<const double *>(nullptr), out, h->ppq);
-    h->nA = h->gA;
-    return SX_OK;
-}
-
-} // namespace
 
 SX_API int sx_cg_shard_open(sx_ctx *ctx, const sx_matrix *A_loc, const double *xa_loc, const double *xs,
                             const double *c_loc, const double *cs, double tol, sx_cg_shard **out, double **reduce_vec) {
@@ -604,33 +661,7 @@ SX_API int sx_cg_shard_open(sx_ctx *ctx, const sx_matrix *A_loc, const double *x
         sx_set_error("out of host memory");
         return SX_ERR_NOMEM;
     }
-    h->ctx = ctx;
-    h->A = A_loc;
-    h->xa = xa_loc;
-    h->xs = xs;
-    h->c = c_loc;
-    h->cs = cs;
-    h->tol = tol;
-    const int64_t m = h->m = A_loc->m, n = h->n = A_loc->n;
-    h->swzT = sx_csc_swizzle(ctx, A_loc);
-    h->swzA = (ctx->opt_xcd_swizzle && A_loc->n_csr_tiles >= 64 && A_loc->csr_imbalance <= SX_SWIZZLE_MAX_IMBALANCE) ? 1 : 0;
-    h->gT = grid_for(ctx, A_loc->n_csc_tiles);
-    h->gA = grid_for(ctx, A_loc->n_csr_tiles);
-    int64_t gv64 = ((m > n ? m : n) + 4 * SX_WG - 1) / (4 * SX_WG);
-    h->gv = static_cast<int>(gv64 < 1 ? 1 : (gv64 > 1024 ? 1024 : gv64));
-    int rc = sx_window_run_csc(ctx, A_loc, &h->win_run);
-    if (rc == SX_OK) rc = sx_rowblock_get(ctx, A_loc, &h->rb);
-    const size_t off_ppq = 256, off_prr = off_ppq + sizeof(double) * CG_GRID, off_vec = off_prr + sizeof(double) * CG_GRID;
-    const size_t bytes = off_vec + sizeof(double) * (4 * static_cast<size_t>(m) + 2 * static_cast<size_t>(n > 0 ? n : 1)) + 256;
-    if (rc == SX_OK && sx_dmalloc(reinterpret_cast<void **>(&h->block), bytes) != hipSuccess) {
-        sx_set_error("hipMalloc of %zu bytes failed for the sharded projector", bytes);
-        rc = SX_ERR_NOMEM;
-    }
-    if (rc != SX_OK) {
-        delete h;
-        return rc;
-    }
-    struct Guard { // a failed launch below must not leak the handle and its block
+    struct Guard { // a failure below must not leak the handle and its block
         sx_cg_shard *h;
         ~Guard() {
             if (h) {
@@ -639,28 +670,29 @@ SX_API int sx_cg_shard_open(sx_ctx *ctx, const sx_matrix *A_loc, const double *x
             }
         }
     } guard{h};
-    h->st = reinterpret_cast<CgState *>(h->block);
-    h->ppq = reinterpret_cast<double *>(h->block + off_ppq);
-    h->prr = reinterpret_cast<double *>(h->block + off_prr);
-    h->z = reinterpret_cast<double *>(h->block + off_vec);
-    h->r = h->z + m;
-    h->p = h->r + m;
-    h->q = h->p + m;
-    h->w = h->q + m;
-    h->atz = h->w + (n > 0 ? n : 1);
-    hipStream_t s = ctx->stream;
-    SX_HIP(hipMemsetAsync(h->st, 0, sizeof(CgState), s));
-    // this rank's share of b = Y v: A_loc (xa^2 .* c) -> q, to be summed over the ranks by the caller
-    if (n > 0) {
-        hipLaunchKernelGGL(k_cg_scale_c, dim3(h->gv), dim3(SX_WG), 0, s, n, xa_loc, c_loc, h->w);
-        SX_TRY(shard_a(h, h->w, h->q));
-    } else {
-        SX_HIP(hipMemsetAsync(h->q, 0, sizeof(double) * static_cast<size_t>(m), s));
+    h->ctx = ctx;
+    h->xa = xa_loc;
+    h->xs = xs;
+    h->c = c_loc;
+    h->cs = cs;
+    h->tol = tol;
+    const int64_t m = A_loc->m, n = A_loc->n;
+    SX_TRY(cg_plan(ctx, A_loc, m > n ? m : n, false, 0, &h->pl));
+    const size_t bytes = plan::layout(m, n).bytes;
+    if (sx_dmalloc(&h->block, bytes) != hipSuccess) {
+        sx_set_error("hipMalloc of %zu bytes failed for the sharded projector", bytes);
+        return SX_ERR_NOMEM;
     }
+    h->b = cg_carve(h->block, m, n);
+    hipStream_t s = ctx->stream;
+    SX_HIP(hipMemsetAsync(h->b.st, 0, sizeof(CgState), s));
+    // this rank's share of b = Y v -> q, to be summed over the ranks by the caller
+    if (n > 0) SX_TRY(cg_rhs(ctx, h->pl, h->b, xa_loc, xs, c_loc, h->b.q));
+    else SX_HIP(hipMemsetAsync(h->b.q, 0, sizeof(double) * static_cast<size_t>(m), s));
     SX_HIP(hipGetLastError());
     guard.h = nullptr;
     *out = h;
-    *reduce_vec = h->q;
+    *reduce_vec = h->b.q;
     return SX_OK;
 }
 
@@ -668,19 +700,16 @@ SX_API int sx_cg_shard_start(sx_cg_shard *h, double *bnorm_out, int *trivial_out
     SX_REQUIRE(h != nullptr, "handle is NULL");
     sx_device_guard guard(h->ctx->device);
     hipStream_t s = h->ctx->stream;
-    const int64_t m = h->m;
-    hipLaunchKernelGGL(k_cg_take_rhs, dim3(h->gv), dim3(SX_WG), 0, s, m, h->q, h->r, h->ppq);
-    if (h->cs) hipLaunchKernelGGL(k_cg_slack_cost, dim3(h->gv), dim3(SX_WG), 0, s, m, h->xs, h->cs, h->r, h->ppq);
-    hipLaunchKernelGGL(k_cg_init, dim3(h->gv), dim3(SX_WG), 0, s, h->st, m, h->ppq, h->gv, h->r, h->p, h->z);
-    CgState host;
-    SX_HIP(hipMemcpyAsync(&host, h->st, sizeof(host), hipMemcpyDeviceToHost, s));
-    SX_HIP(hipStreamSynchronize(s));
-    h->bnrm = sqrt(host.rho[0]);
-    const bool trivial = !(h->bnrm > h->tol) || (h->bnrm < h->tol * h->bnrm);
-    hipLaunchKernelGGL(k_cg_set_atol, dim3(1), dim3(1), 0, s, h->st, h->tol * h->bnrm, trivial ? 1 : 0);
+    const CgBufs &b = h->b;
+    const int gv = h->pl.gv;
+    // the reduced right-hand side (against the single device's fused row pass): r = q, then the slack cost
+    hipLaunchKernelGGL(k_cg_take_rhs, dim3(gv), dim3(SX_WG), 0, s, b.len, b.q, b.r, b.ppq);
+    if (h->cs) hipLaunchKernelGGL(k_cg_slack_cost, dim3(gv), dim3(SX_WG), 0, s, b.len, h->xs, h->cs, b.r, b.ppq);
+    plan::Start start;
+    SX_TRY(cg_begin(h->ctx, h->pl, b, gv, h->tol, plan::start_sharded, &h->bnrm, &start));
     SX_HIP(hipGetLastError());
     if (bnorm_out) *bnorm_out = h->bnrm;
-    if (trivial_out) *trivial_out = trivial ? 1 : 0;
+    if (trivial_out) *trivial_out = start.trivial ? 1 : 0;
     return SX_OK;
 }
 
@@ -688,24 +717,25 @@ SX_API int sx_cg_shard_start(sx_cg_shard *h, double *bnorm_out, int *trivial_out
 SX_API int sx_cg_shard_local(sx_cg_shard *h) {
     SX_REQUIRE(h != nullptr, "handle is NULL");
     sx_device_guard guard(h->ctx->device);
-    if (h->n > 0) {
-        shard_at(h, h->p, h->xa, h->w);
-        SX_TRY(shard_a(h, h->w, h->q));
+    if (h->pl.A->n > 0) {
+        cg_cols(h->ctx, h->pl, h->b, h->b.p, h->xa, h->b.w);
+        SX_TRY(cg_rows(h->ctx, h->pl, h->b, h->b.w, h->xs, nullptr, h->b.q));
+    } else { // an empty block adds nothing to the sum; q still holds the last reduced vector
+        SX_HIP(hipMemsetAsync(h->b.q, 0, sizeof(double) * static_cast<size_t>(h->b.len), h->ctx->stream));
     }
     SX_HIP(hipGetLastError());
     return SX_OK;
 }
 
-// with q reduced over the ranks: q += xs^2 .* p, alpha, z, r, beta, p  (iteration number = parity of rho's slot)
+// with q reduced over the ranks: q += xs^2 .* p (against the single device's fused slack term), alpha, z, r, beta, p
+// (iteration number = parity of rho's slot)
 SX_API int sx_cg_shard_update(sx_cg_shard *h, int parity) {
     SX_REQUIRE(h != nullptr, "handle is NULL");
     sx_device_guard guard(h->ctx->device);
-    hipStream_t s = h->ctx->stream;
-    const int64_t m = h->m;
-    hipLaunchKernelGGL(k_cg_add_slack, dim3(h->gv), dim3(SX_WG), 0, s, h->st, m, h->xs, h->p, h->q, h->ppq);
-    hipLaunchKernelGGL(k_cg_update_zr, dim3(h->gv), dim3(SX_WG), 0, s, h->st, parity & 1, m, h->ppq, h->gv, h->p, h->q, h->z,
-                       h->r, h->prr);
-    hipLaunchKernelGGL(k_cg_update_p, dim3(h->gv), dim3(SX_WG), 0, s, h->st, parity & 1, m, h->prr, h->gv, h->r, h->p);
+    const CgBufs &b = h->b;
+    const int gv = h->pl.gv;
+    hipLaunchKernelGGL(k_cg_add_slack, dim3(gv), dim3(SX_WG), 0, h->ctx->stream, b.st, b.len, h->xs, b.p, b.q, b.ppq);
+    cg_update(h->ctx, h->pl, b, parity & 1, gv, gv);
     SX_HIP(hipGetLastError());
     return SX_OK;
 }
@@ -714,8 +744,7 @@ SX_API int sx_cg_shard_poll(sx_cg_shard *h, int *done, int64_t *iters) {
     SX_REQUIRE(h != nullptr, "handle is NULL");
     sx_device_guard guard(h->ctx->device);
     CgState host;
-    SX_HIP(hipMemcpyAsync(&host, h->st, sizeof(host), hipMemcpyDeviceToHost, h->ctx->stream));
-    SX_HIP(hipStreamSynchronize(h->ctx->stream));
+    SX_TRY(cg_poll(h->ctx, h->b, &host));
     if (done) *done = host.done;
     if (iters) *iters = host.iters;
     return SX_OK;
@@ -727,43 +756,27 @@ SX_API int sx_cg_shard_finish(sx_cg_shard *h, double *proj_cols_loc, double *pro
                               double *rows_sumsq, sx_cg_result *result) {
     SX_REQUIRE(h != nullptr, "handle is NULL");
     sx_device_guard guard(h->ctx->device);
-    hipStream_t s = h->ctx->stream;
-    const int64_t m = h->m, n = h->n;
-    CgState host;
-    SX_HIP(hipMemcpyAsync(&host, h->st, sizeof(host), hipMemcpyDeviceToHost, s));
-    SX_HIP(hipStreamSynchronize(s));
-    const long long iters = host.iters;
-    const int converged = host.converged;
-    const double rel = h->bnrm > 0 ? sqrt(host.rho[host.iters & 1]) / h->bnrm : 0.0;
-    hipLaunchKernelGGL(k_cg_set_atol, dim3(1), dim3(1), 0, s, h->st, h->tol * h->bnrm, 0); // re-arm the kernels
-    double cols = 0.0, rows = 0.0;
-    if (n > 0) {
-        hipLaunchKernelGGL(k_cg_ones, dim3(h->gv), dim3(SX_WG), 0, s, n, h->w);
-        shard_at(h, h->z, h->w, h->atz);
-        hipLaunchKernelGGL(k_cg_proj_cols, dim3(h->gv), dim3(SX_WG), 0, s, n, h->xa, h->c, h->atz, h->ppq, proj_cols_loc);
-    } else {
-        SX_HIP(hipMemsetAsync(h->ppq, 0, sizeof(double) * h->gv, s));
-    }
-    hipLaunchKernelGGL(k_cg_proj_rows, dim3(h->gv), dim3(SX_WG), 0, s, m, h->xs, h->cs, h->z, h->prr, proj_rows);
+    sx_ctx *ctx = h->ctx;
+    hipStream_t s = ctx->stream;
+    const CgBufs &b = h->b;
+    const int gv = h->pl.gv;
+    CgState loop, host;
+    SX_TRY(cg_poll(ctx, b, &loop));
+    SX_TRY(cg_project(ctx, h->pl, b, h->xa, h->xs, h->c, h->cs, h->tol * h->bnrm, proj_cols_loc, proj_rows));
     // the two sums separately: k_cg_finish adds them, so run it once per term against a zeroed partner
-    SX_HIP(hipMemsetAsync(h->w, 0, sizeof(double), s));
-    hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(SX_WG), 0, s, h->st, h->ppq, h->gv, h->w, 1);
-    SX_HIP(hipMemcpyAsync(&host, h->st, sizeof(host), hipMemcpyDeviceToHost, s));
-    SX_HIP(hipStreamSynchronize(s));
-    cols = host.sumsq;
-    hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(SX_WG), 0, s, h->st, h->prr, h->gv, h->w, 1);
-    SX_HIP(hipMemcpyAsync(&host, h->st, sizeof(host), hipMemcpyDeviceToHost, s));
-    SX_HIP(hipStreamSynchronize(s));
-    rows = host.sumsq;
+    SX_HIP(hipMemsetAsync(b.w, 0, sizeof(double), s));
+    hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(SX_WG), 0, s, b.st, b.ppq, gv, b.w, 1);
+    SX_TRY(cg_poll(ctx, b, &host));
+    const double cols = host.sumsq;
+    hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(SX_WG), 0, s, b.st, b.prr, gv, b.w, 1);
+    SX_TRY(cg_poll(ctx, b, &host));
+    const double rows = host.sumsq;
     SX_HIP(hipGetLastError());
     if (cols_sumsq) *cols_sumsq = cols;
     if (rows_sumsq) *rows_sumsq = rows;
     if (result) {
         memset(result, 0, sizeof(*result));
-        result->b_norm = h->bnrm;
-        result->iters = iters;
-        result->converged = converged;
-        result->rel_residual = rel;
+        cg_result(loop, h->bnrm, false, result); // trivial went to the caller at start: converged is the loop's own flag
     }
     return SX_OK;
 }
@@ -887,36 +900,32 @@ SX_API int sx_projector_free_dev(sx_ctx *ctx, const sx_matrix *A, int64_t nf, co
     const int64_t m = A->m, n = A->n;
     hipStream_t s = ctx->stream;
     sx_stage tmp(ctx); // device temporaries, freed on return
-    void *v_isfree, *v_stats, *v_cfree, *v_t, *v_r, *v_p, *v_g, *v_w, *v_cadj, *v_xa2, *v_cs, *v_ones, *v_st, *v_pa, *v_pb;
-    SX_TRY(tmp.in(nullptr, static_cast<size_t>(n), &v_isfree));
-    SX_TRY(tmp.in(nullptr, 4 * sizeof(unsigned long long), &v_stats));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * nf, &v_cfree));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * nf, &v_t));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * nf, &v_r));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * nf, &v_p));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * nf, &v_g));   // A_2^T w  (nf)
-    SX_TRY(tmp.in(nullptr, sizeof(double) * m, &v_w));    // A_2 p, later g = A_2 t  (m)
-    SX_TRY(tmp.in(nullptr, sizeof(double) * n, &v_cadj));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * n, &v_xa2));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * m, &v_cs));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * nf, &v_ones));
-    SX_TRY(tmp.in(nullptr, 256, &v_st));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * CG_GRID, &v_pa));
-    SX_TRY(tmp.in(nullptr, sizeof(double) * CG_GRID, &v_pb));
-    uint8_t *is_free = static_cast<uint8_t *>(v_isfree);
-    unsigned long long *stats = static_cast<unsigned long long *>(v_stats);
-    double *c_free = static_cast<double *>(v_cfree), *t = static_cast<double *>(v_t), *r = static_cast<double *>(v_r);
-    double *p = static_cast<double *>(v_p), *g = static_cast<double *>(v_g), *w = static_cast<double *>(v_w);
-    double *c_adj = static_cast<double *>(v_cadj), *xa2 = static_cast<double *>(v_xa2), *cs = static_cast<double *>(v_cs);
-    double *ones = static_cast<double *>(v_ones), *pa = static_cast<double *>(v_pa), *pb = static_cast<double *>(v_pb);
-    CgState *st = static_cast<CgState *>(v_st);
-    auto g1 = [](int64_t k) {
-        int64_t b = (k + 4 * SX_WG - 1) / (4 * SX_WG);
-        return dim3(static_cast<unsigned>(b < 1 ? 1 : (b > 1024 ? 1024 : b)));
-    };
+    uint8_t *is_free;
+    unsigned long long *stats;
+    double *c_free, *c_adj, *xa2, *cs, *ones;
+    unsigned char *st_block;
+    CgBufs b; // of the inner CG on nf-vectors: z is t, q is A_2^T w; w (m) is A_2 p, later g = A_2 t; atz unused
+    b.len = nf;
+    SX_TRY(tmp.tmp(n, &is_free));
+    SX_TRY(tmp.tmp(4, &stats));
+    SX_TRY(tmp.tmp(nf, &c_free));
+    SX_TRY(tmp.tmp(nf, &b.z));
+    SX_TRY(tmp.tmp(nf, &b.r));
+    SX_TRY(tmp.tmp(nf, &b.p));
+    SX_TRY(tmp.tmp(nf, &b.q));
+    SX_TRY(tmp.tmp(m, &b.w));
+    SX_TRY(tmp.tmp(n, &c_adj));
+    SX_TRY(tmp.tmp(n, &xa2));
+    SX_TRY(tmp.tmp(m, &cs));
+    SX_TRY(tmp.tmp(nf, &ones));
+    SX_TRY(tmp.tmp(256, &st_block)); // the state, in a block of 256 bytes
+    SX_TRY(tmp.tmp(CG_GRID, &b.ppq));
+    SX_TRY(tmp.tmp(CG_GRID, &b.prr));
+    b.st = reinterpret_cast<CgState *>(st_block);
+    auto g1 = [](int64_t k) { return dim3(static_cast<unsigned>(plan::vector_grid(k))); };
     SX_HIP(hipMemsetAsync(is_free, 0, static_cast<size_t>(n), s));
     SX_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), s));
-    SX_HIP(hipMemsetAsync(st, 0, sizeof(CgState), s));
+    SX_HIP(hipMemsetAsync(b.st, 0, sizeof(CgState), s));
     hipLaunchKernelGGL(k_free_flags, g1(nf), dim3(SX_WG), 0, s, nf, free_idx, is_free);
 
     // ---- t = cg(A_2^T A_2, c_free): the CG kernels with the row pass first (w = A_2 p, alpha = rho / (w.w))
@@ -927,42 +936,28 @@ SX_API int sx_projector_free_dev(sx_ctx *ctx, const sx_matrix *A, int64_t nf, co
         ~Guard() { (void)sx_matrix_destroy(M); }
     } guard{A2};
     SX_TRY(sx_gather_f64_dev(ctx, nf, free_idx, c, c_free));
-    const int swzT = sx_csc_swizzle(ctx, A2);
-    const int swzA = (ctx->opt_xcd_swizzle && A2->n_csr_tiles >= 64 && A2->csr_imbalance <= SX_SWIZZLE_MAX_IMBALANCE) ? 1 : 0;
-    const int gT = grid_for(ctx, A2->n_csc_tiles), gA = grid_for(ctx, A2->n_csr_tiles);
-    const dim3 gv = g1(nf);
-    hipLaunchKernelGGL(k_cg_ones, gv, dim3(SX_WG), 0, s, nf, ones);
-    hipLaunchKernelGGL(k_cg_take_rhs, gv, dim3(SX_WG), 0, s, nf, c_free, r, pa);             // r = c_free, partials r.r
-    hipLaunchKernelGGL(k_cg_init, gv, dim3(SX_WG), 0, s, st, nf, pa, static_cast<int>(gv.x), r, p, t);
+    CgPlan pl; // plain walks: nothing is built for a block that lives for this call
+    SX_TRY(cg_plan(ctx, A2, nf, true, 0, &pl));
+    hipLaunchKernelGGL(k_cg_ones, dim3(pl.gv), dim3(SX_WG), 0, s, nf, ones);
+    hipLaunchKernelGGL(k_cg_take_rhs, dim3(pl.gv), dim3(SX_WG), 0, s, nf, c_free, b.r, b.ppq); // r = c_free, partials r.r
+    double bn = 0.0;
+    plan::Start start;
+    SX_TRY(cg_begin(ctx, pl, b, pl.gv, 1e-8, plan::start_single, &bn, &start));
     CgState host;
-    SX_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-    SX_HIP(hipStreamSynchronize(s));
-    const double bn = sqrt(host.rho[0]);
-    const bool trivial = !(bn > 1e-8);
-    hipLaunchKernelGGL(k_cg_set_atol, dim3(1), dim3(1), 0, s, st, 1e-8 * bn, trivial ? 1 : 0);
-    if (!trivial) {
-        for (int it = 0; it < 1000; ++it) {
-            hipLaunchKernelGGL(k_cg_a, dim3(gA), dim3(SX_WG), 0, s, st, A2->csr_tiles, A2->n_csr_tiles, swzA, A2->csr_ptr,
-                               A2->csr_idx, A2->csr_val, p, static_cast<const double *>(nullptr),
-                               static_cast<const double *>(nullptr), w, pa);                 // w = A_2 p, partials w.w
-            hipLaunchKernelGGL(k_cg_at, dim3(gT), dim3(SX_WG), 0, s, st, A2->csc_tiles, A2->n_csc_tiles, swzT, A2->csc_ptr,
-                               A2->csc_idx, A2->csc_val, w, ones, g);                        // g = A_2^T w
-            hipLaunchKernelGGL(k_cg_update_zr, gv, dim3(SX_WG), 0, s, st, it & 1, nf, pa, gA, p, g, t, r, pb);
-            hipLaunchKernelGGL(k_cg_update_p, gv, dim3(SX_WG), 0, s, st, it & 1, nf, pb, static_cast<int>(gv.x), r, p);
-            if ((it % 25) == 24) {
-                SX_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-                SX_HIP(hipStreamSynchronize(s));
-                if (host.done) break;
-            }
+    for (int it = 0; start.run && it < 1000; ++it) {
+        SX_TRY(cg_rows(ctx, pl, b, b.p, nullptr, nullptr, b.w)); // w = A_2 p, partials w.w
+        cg_cols(ctx, pl, b, b.w, ones, b.q);                     // q = A_2^T w
+        cg_update(ctx, pl, b, it & 1, pl.nA, pl.gv);
+        if ((it % 25) == 24) {
+            SX_TRY(cg_poll(ctx, b, &host));
+            if (host.done) break;
         }
     }
     // ---- g = A_2 t (m-vector), adjusted cost c - A^T g on the structurals (zero on the free ones), -g on the slacks
-    hipLaunchKernelGGL(k_cg_set_atol, dim3(1), dim3(1), 0, s, st, 0.0, 0);                   // re-arm
-    hipLaunchKernelGGL(k_cg_a, dim3(gA), dim3(SX_WG), 0, s, st, A2->csr_tiles, A2->n_csr_tiles, swzA, A2->csr_ptr,
-                       A2->csr_idx, A2->csr_val, t, static_cast<const double *>(nullptr), static_cast<const double *>(nullptr),
-                       w, pa);
-    SX_TRY(sx_score_columns_dev(ctx, A, w, c, nullptr, nullptr, nullptr, 0.0, c_adj, nullptr));
-    hipLaunchKernelGGL(k_free_slack_cost, g1(m), dim3(SX_WG), 0, s, m, row_lt, w, cs);
+    cg_arm(ctx, b, 0.0, 0); // re-arm
+    SX_TRY(cg_rows(ctx, pl, b, b.z, nullptr, nullptr, b.w));
+    SX_TRY(sx_score_columns_dev(ctx, A, b.w, c, nullptr, nullptr, nullptr, 0.0, c_adj, nullptr));
+    hipLaunchKernelGGL(k_free_slack_cost, g1(m), dim3(SX_WG), 0, s, m, row_lt, b.w, cs);
     // ---- scale of the free columns
     hipLaunchKernelGGL(k_free_column_stats, g1(n), dim3(SX_WG), 0, s, n, A->csc_ptr, A->csc_val, is_free, xa, stats);
     hipLaunchKernelGGL(k_free_max, g1(m), dim3(SX_WG), 0, s, m, xs, stats + 3);
@@ -979,11 +974,10 @@ SX_API int sx_projector_free_dev(sx_ctx *ctx, const sx_matrix *A, int64_t nf, co
     // ---- the penalised projector, then the norm over the QP's own variables (non-free columns, '<' rows)
     SX_TRY(sx_projector_std_dev(ctx, A, xa2, xs, c_adj, cs, 1e-8, 1000, proj_cols, proj_rows, result));
     const dim3 gn = g1(n), gm = g1(m);
-    hipLaunchKernelGGL(k_free_norm, gn, dim3(SX_WG), 0, s, n, is_free, 0, proj_cols, pa);
-    hipLaunchKernelGGL(k_free_norm, gm, dim3(SX_WG), 0, s, m, row_lt, 1, proj_rows, pb);
-    hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(SX_WG), 0, s, st, pa, static_cast<int>(gn.x), pb, static_cast<int>(gm.x));
-    SX_HIP(hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s));
-    SX_HIP(hipStreamSynchronize(s));
+    hipLaunchKernelGGL(k_free_norm, gn, dim3(SX_WG), 0, s, n, is_free, 0, proj_cols, b.ppq);
+    hipLaunchKernelGGL(k_free_norm, gm, dim3(SX_WG), 0, s, m, row_lt, 1, proj_rows, b.prr);
+    hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(SX_WG), 0, s, b.st, b.ppq, static_cast<int>(gn.x), b.prr, static_cast<int>(gm.x));
+    SX_TRY(cg_poll(ctx, b, &host));
     SX_HIP(hipGetLastError());
     result->proj_norm = sqrt(host.sumsq);
     return SX_OK;

@@ -226,6 +226,11 @@ constexpr double SX_SWIZZLE_MAX_IMBALANCE = 1.5;
 inline int sx_csc_swizzle(const sx_ctx *ctx, const sx_matrix *A) {
     return (ctx->opt_xcd_swizzle && A->n_csc_tiles >= 64 && !A->csc_swizzle_off) ? 1 : 0;
 }
+// the same for A's ROW walks of the CG (K4): the context's option, unless the eight tile ranges are too uneven.  K2
+// (sx_lp_kernels.hip, launch of k_score_rows) has a rule of its own without the >= 64 test and does not come here.
+inline int sx_csr_swizzle(const sx_ctx *ctx, const sx_matrix *A) {
+    return (ctx->opt_xcd_swizzle && A->n_csr_tiles >= 64 && A->csr_imbalance <= SX_SWIZZLE_MAX_IMBALANCE) ? 1 : 0;
+}
 // grid of a launch with one workgroup per item: under the XCD-contiguous map (sx_tile_of_block, sx_segwalk.h) every XCD
 // gets ceil(n / 8) slots, and the workgroups of the last slots that map past n return at once
 inline unsigned sx_xcd_grid(int64_t n, int swizzle) {
@@ -281,6 +286,14 @@ struct sx_stage {
         if (src) SX_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
         *out = p;
         return SX_OK;
+    }
+    // an uninitialised temporary of `count` elements
+    template <class T>
+    int tmp(size_t count, T **out) {
+        void *p = nullptr;
+        const int rc = in(nullptr, sizeof(T) * count, &p);
+        *out = static_cast<T *>(p);
+        return rc;
     }
     int out(void *dst_host, const void *src_dev, size_t bytes) {
         if (dst_host && bytes)

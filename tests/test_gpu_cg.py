@@ -121,6 +121,129 @@ def test_projector_window_option_never_changes_results(ctx):
         assert np.array_equal(out[window][1].view(np.uint64), out[0][1].view(np.uint64)), window
 
 
+def make_cut_lp():
+    """The LP of test_projector_trivial_and_maxiter at x = 0.5 with the CG cut at 7 iterations (tol 1e-14), and the CPU
+    statement of that run without and with a cost on the slack columns.  Computed once; nobody writes to it."""
+    inst = workloads.sparse_lp(100, 400, 4, seed=5, stratified=False)
+    m, n = inst.A.shape
+    xx = L.standard_x(inst.A, inst.b, inst.sense, np.full(n, 0.5))
+    rows = L.slack_rows(inst.sense)
+    xs = np.zeros(m)
+    xs[rows] = xx[n:]
+    cs = np.random.default_rng(31).standard_normal(m)
+    proj, it = L.projector_matrix_free(inst.A, inst.sense, xx, L.standard_c(inst.c, inst.sense), tol=1e-14, maxiter=7)
+    proj_cs, it_cs = L.projector_matrix_free(inst.A, inst.sense, xx, np.concatenate([inst.c, cs[rows]]), tol=1e-14, maxiter=7)
+    assert it == 7 and it_cs == 7
+    return dict(A=inst.A, c=inst.c, sense=inst.sense, xa=xx[:n], xs=xs, cs=cs, rows=rows, proj=proj, proj_cs=proj_cs)
+
+
+@pytest.fixture(scope="module")
+def cut_lp():
+    return make_cut_lp()
+
+
+def sharded_projector(ctx, lp, blocks, cs=None, tol=1e-14, maxiter=7):
+    """sx_cg_shard_* the way ShardedLP.projector_norm drives it, with both ranks' handles on one context: open, sum,
+    start, maxiter x (local, sum, update), poll, finish with both projection vectors requested.  The all-reduce: the
+    two reduce vectors are read through the pointers sx_cg_shard_open returned, added (one IEEE addition per element,
+    as the collective's SUM over two ranks) and the sum is written to both."""
+    import ctypes as C
+    from smart_crossover.hip import lib as _l
+    lib, m = ctx._lib, lp["A"].shape[0]
+    csc = lp["A"].tocsc()
+    d_xs, d_cs = ctx.to_device(lp["xs"]), (ctx.to_device(cs) if cs is not None else None)
+    ranks = []
+    for lo, hi in blocks:
+        r = dict(A=ctx.matrix(sp.csr_matrix(csc[:, lo:hi])), xa=ctx.to_device(lp["xa"][lo:hi]), c=ctx.to_device(lp["c"][lo:hi]),
+                 pc=ctx.empty(hi - lo, np.float64), pr=ctx.empty(m, np.float64))
+        h, vec = C.c_void_p(), C.c_void_p()
+        _l.check(lib.sx_cg_shard_open(ctx.handle, r["A"].handle, r["xa"].ptr, d_xs.ptr, r["c"].ptr,
+                                      d_cs.ptr if d_cs is not None else None, float(tol), C.byref(h), C.byref(vec)))
+        r["h"], r["q"] = h, ctx.wrap(vec.value, m, np.float64)
+        ranks.append(r)
+
+    def allreduce():
+        total = ranks[0]["q"].download() + ranks[1]["q"].download()
+        for r in ranks:
+            r["q"].upload(total)
+
+    try:
+        allreduce()
+        for r in ranks:
+            bn, tr = C.c_double(0), C.c_int(0)
+            _l.check(lib.sx_cg_shard_start(r["h"], C.byref(bn), C.byref(tr)))
+            r["bnorm"], r["trivial"] = bn.value, tr.value
+        for k in range(maxiter):
+            for r in ranks:
+                _l.check(lib.sx_cg_shard_local(r["h"]))
+            allreduce()
+            for r in ranks:
+                _l.check(lib.sx_cg_shard_update(r["h"], k & 1))
+        for r in ranks:
+            d, it = C.c_int(0), C.c_int64(0)
+            _l.check(lib.sx_cg_shard_poll(r["h"], C.byref(d), C.byref(it)))
+            cols, rws, res = C.c_double(0), C.c_double(0), _l.CgResult()
+            _l.check(lib.sx_cg_shard_finish(r["h"], r["pc"].ptr, r["pr"].ptr, C.byref(cols), C.byref(rws), C.byref(res)))
+            r.update(done=d.value, polled=it.value, cols=cols.value, rows=rws.value, iters=int(res.iters),
+                     converged=int(res.converged), proj_cols=r["pc"].download(), proj_rows=r["pr"].download())
+    finally:
+        for r in ranks:
+            lib.sx_cg_shard_close(r["h"])
+            r["A"].free()
+    return ranks
+
+
+def check_sharded(ranks, lp, want):
+    n = lp["A"].shape[1]
+    for r in ranks:
+        assert r["trivial"] == 0 and r["iters"] == 7 and r["polled"] == 7 and r["converged"] == 0
+    assert np.float64(ranks[0]["rows"]).view(np.uint64) == np.float64(ranks[1]["rows"]).view(np.uint64)
+    norm = float(np.sqrt(ranks[0]["cols"] + ranks[1]["cols"] + ranks[0]["rows"]))
+    assert norm == pytest.approx(float(np.linalg.norm(want)), rel=1e-9)
+    got_cols = np.concatenate([ranks[0]["proj_cols"], ranks[1]["proj_cols"]])
+    np.testing.assert_allclose(got_cols, want[:n], rtol=0, atol=1e-9 * np.abs(want[:n]).max())
+    for r in ranks:      # the slack rows are replicated; rows without a slack column project to zero
+        np.testing.assert_allclose(r["proj_rows"][lp["rows"]], want[n:], rtol=0, atol=1e-9 * np.abs(want[n:]).max())
+        assert not np.any(np.delete(r["proj_rows"], lp["rows"]))
+
+
+@pytest.mark.parametrize("blocks", [((0, 250), (250, 400)), ((0, 400), (400, 400))], ids=["250+150", "400+empty"])
+def test_sharded_cg_in_one_process_matches_cpu(ctx, cut_lp, blocks):
+    """Two sx_cg_shard handles on one context play two ranks (the second case: one rank holds every column, the other
+    an empty block), cut at 7 iterations like test_projector_trivial_and_maxiter, whose rel = 1e-9 against the CPU
+    statement is the tolerance here too; finish is asked for both projection vectors.  The rank with the empty block
+    must hand zeros to every sum: a reduce vector left as the last sum gave ||proj|| = 11.837 against 9.572 here."""
+    check_sharded(sharded_projector(ctx, cut_lp, blocks), cut_lp, cut_lp["proj"])
+
+
+def test_sharded_cg_with_slack_cost_matches_cpu(ctx, cut_lp):
+    """The same run with a cost on the slack columns (cs != NULL), against the CPU statement given [c; cs_<]."""
+    check_sharded(sharded_projector(ctx, cut_lp, ((0, 250), (250, 400)), cs=cut_lp["cs"]), cut_lp, cut_lp["proj_cs"])
+
+
+def test_free_branch_is_bit_equal_across_graph_settings(ctx, cut_lp):
+    """sx_projector_free_dev with the first 5 columns free: its inner CG launches directly, the penalised projector it
+    ends with replays graph batches or not by option "graph" -- an execution detail, so every result is the same bit
+    for bit."""
+    m, n = cut_lp["A"].shape
+    dA = ctx.matrix(cut_lp["A"])
+    args = (ctx.to_device(np.arange(5, dtype=np.int64)), ctx.to_device(cut_lp["xa"]), ctx.to_device(cut_lp["xs"]),
+            ctx.to_device(cut_lp["c"]), ctx.to_device((cut_lp["sense"] == "<").astype(np.uint8)))
+    out = {}
+    try:
+        for flag in (0, 1):
+            ctx.set_option("graph", flag)
+            pc, pr = ctx.empty(n, np.float64), ctx.empty(m, np.float64)
+            r = ctx.projector_free(dA, *args, pc, pr)
+            out[flag] = ((r.proj_norm, int(r.iters), int(r.converged)), pc.download())
+    finally:
+        ctx.set_option("graph", 1)
+        dA.free()
+    assert np.isfinite(out[0][0][0]) and out[0][0][1] >= 1
+    assert out[0][0] == out[1][0]
+    assert np.array_equal(out[0][1].view(np.uint64), out[1][1].view(np.uint64))
+
+
 def test_projector_config2_size_hits_cap(ctx, capsys):
     """Config 2 (2e4 x 1e5): the reference's CG runs into maxiter=1000 here and its
     result then depends on rounding order; the device must finish, report 1000 iterations and land
