@@ -91,7 +91,9 @@ int sx_ctx_sync(sx_ctx *ctx);
  * tree arrays and potentials of the network simplex in LDS when they fit, V <= 4480), "ns_block" (arcs priced
  * per lane and block by the network simplex: 0 = by size [default], 1..64), "netdual" (sx_netdual_dev: -1 / 1 =
  * run whenever problem and basis are in its domain [default], 0 = always answer status 5) and "nd_grid"
- * (workgroups of its cooperative grid: 0 = by size [default], 1..256).
+ * (workgroups of its cooperative grid: 0 = by size [default], 1..256),
+ * "band_setup" (sx_crossover_band_*_dev: who matches the basic columns to the band rows and assembles the band: 0 = the
+ * host, csrc/sx_band_plan.h [default], 1 = the device, sx_band_match_dev + sx_band_triplets_dev; the same basis either way).
  * Unknown keys return SX_ERR_INVALID. */
 int sx_ctx_set_option(sx_ctx *ctx, const char *key, int64_t value);
 /* name (e.g. "gfx950:sramecc+:xnack-"), CU count and total HBM bytes of the context's device */
@@ -580,6 +582,24 @@ int sx_crossover_band_basis_dev(sx_ctx *ctx, const sx_matrix *A, const double *b
                                 const double *u, const uint8_t *row_is_lt, const double *x_start, const int8_t *vbasis_in,
                                 const int8_t *cbasis_in, int64_t max_iter, double feas_tol, double opt_tol, double *x,
                                 double *y, int8_t *vbasis, int8_t *cbasis, sx_simplex_result *result);
+/* Two stages of that set-up on the device (csrc/sx_band_match.hip); the crossover takes them instead of their host
+ * statements under context option "band_setup" = 1 (0, the default: host) or SX_BAND_SETUP=device|host in the environment,
+ * which overrides the option.  Blocking; arrays device unless named host.
+ * sx_band_match_dev restates sx_plan::match_columns_to_rows (csrc/sx_band_plan.h), same order and constants: every band row
+ * gets at most one basic variable.  is_basic[n + m] (variables: columns of A, then n + i the logical of row i); rowb[m]: row
+ * -> band position in [0, m1), -1 for a dense row; prev_pos[m1] or NULL: the variable that sat on the position last time
+ * (-1: none; a variable at most once).  Out: bvar[m1] the variable on the position (-1: none), placed[n + m],
+ * *rounds_host (may be NULL): mutual-best rounds that placed a column after the seeds and the first round.  The result is
+ * the host's, bit for bit, whatever the schedule. */
+int sx_band_match_dev(sx_ctx *ctx, const sx_matrix *A, const uint8_t *is_basic, const int32_t *rowb, int64_t m1,
+                      const int64_t *prev_pos, int64_t *bvar, uint8_t *placed, int64_t *rounds_host);
+/* sx_band_triplets_dev restates sx_plan::walk_band + sx_plan::band_triplets (csrc/sx_band_plan.h): the triplets
+ * sx_bandlu_create_dev takes and the widths of the band.  bvar[m1]: the variable on each position of the epoch (-1
+ * placeholder, -2 padding, >= n a logical: each the unit vector of its position); rowb[m]: row -> position, -1 for a border
+ * row.  row = col = val = NULL: *count_host, *kl_host, *ku_host only; else the count triplets are written (cap: room in row /
+ * col / val, SX_ERR_INVALID when too small), in the order of the host walk. */
+int sx_band_triplets_dev(sx_ctx *ctx, const sx_matrix *A, int64_t m1, const int64_t *bvar, const int32_t *rowb, int64_t cap,
+                         int32_t *row, int32_t *col, double *val, int64_t *count_host, int *kl_host, int *ku_host);
 
 /* Network simplex (K16n) for the re-solves of the network crossover (network_methods/net_manager.py:211-222
  * solve_subproblem -> solve_mcf / solve_ot with warm_start_basis; the reference hands these to Gurobi's /

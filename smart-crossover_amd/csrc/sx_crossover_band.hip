@@ -27,7 +27,8 @@
 // (Epoch: device arrays, factors, border operators, tableau -- owned in one place); then one function per stage, and
 // crossover_band_impl, which is the list of the stages and the three ways an epoch goes round again.  The host set-up
 // between the device stages -- row order, matching, block geometry, triplets, the bookkeeping after the two LUs -- is
-// sx_band_plan.h: plain C++ over vectors, tested on the CPU, and the seam a device-side set-up would replace.
+// sx_band_plan.h: plain C++ over vectors, tested on the CPU, and the seam a device-side set-up replaces stage by stage -- under
+// context option "band_setup" (SX_BAND_SETUP=device) the matching and the band assembly are sx_band_match.hip's kernels.
 #include "sx_internal.h"
 #include "sx_border.h"
 #include "sx_band_plan.h"
@@ -1091,6 +1092,8 @@ struct BandCall {
     const double *b = nullptr, *c = nullptr; // (device)
     hipStream_t s = nullptr;
     bool trace = false, given = false;
+    bool dev_setup = false; // columns are matched and the band is assembled on the device (sx_band_match.hip; option "band_setup")
+    int32_t *d_rowb = nullptr; // [m] the call's row -> band position, uploaded for the first device matching
     double t_begin = 0.0;
     int64_t m = 0, n = 0, max_iter = 0;
     double feas_tol = 0.0, opt_tol = 0.0;
@@ -1137,7 +1140,10 @@ struct Epoch {
     // the plan (sx_band_plan.h)
     pl::Matching mt;
     pl::EpochGeometry g;
-    pl::BandTriplets tri;
+    pl::BandTriplets tri;      // (device set-up: kl and ku only, the triplets never come to the host)
+    int64_t tri_count = 0;     // triplets of the band
+    int64_t *d_gbvar = nullptr; // device set-up: the epoch's g.bvar and g.rowb
+    int32_t *d_growb = nullptr;
     std::vector<int32_t> ph_row; // the row whose unit vector a placeholder is
     pl::Border bd;
     std::vector<int64_t> head;
@@ -1359,20 +1365,61 @@ int call_blocks(BandCall &C, int64_t ndr0, size_t ntracked) {
 }
 
 // ---------------------------------------------------------------------------------------------- stages of an epoch
-// blocks, the epoch's row maps on the device, band triplets
+// every band row gets at most one basic variable: sx_band_plan.h on the host copies, or sx_band_match.hip on the resident
+// matrix (O(n + m) bytes go up, bvar and placed come down: the stages behind this one read them on the host)
+int match_columns(BandCall &C, const HostLp &lp, const pl::RowPlan &rp, const pl::BasisState &bs, Epoch &E) {
+    int64_t rounds = 0;
+    if (!C.dev_setup) pl::match_columns_to_rows(lp.csc(), rp, bs.is_basic, bs.prev_pos, E.mt);
+    else {
+        const size_t m1 = rp.rows_band.size();
+        if (!C.d_rowb) {
+            SX_TRY(C.dev.get(rp.rowb.size(), &C.d_rowb));
+            SX_TRY(up(C.s, C.d_rowb, rp.rowb));
+        }
+        uint8_t *d_isb = nullptr, *d_placed = nullptr;
+        int64_t *d_prev = nullptr, *d_bvar = nullptr;
+        DevBufs tdev;
+        SX_TRY(tdev.get(bs.is_basic.size(), &d_isb));
+        SX_TRY(tdev.get(bs.is_basic.size(), &d_placed));
+        SX_TRY(tdev.get(m1, &d_prev));
+        SX_TRY(tdev.get(m1, &d_bvar));
+        SX_TRY(up(C.s, d_isb, bs.is_basic));
+        SX_TRY(up(C.s, d_prev, bs.prev_pos));
+        SX_TRY(sx_band_match_dev(C.ctx, C.A, d_isb, C.d_rowb, static_cast<int64_t>(m1), bs.prev_pos.empty() ? nullptr : d_prev, d_bvar, d_placed, &rounds));
+        SX_TRY(down(C.s, E.mt.bvar, d_bvar, m1));
+        SX_TRY(down(C.s, E.mt.placed, d_placed, bs.is_basic.size()));
+        SX_HIP(hipStreamSynchronize(C.s));
+    }
+    if (C.trace) {
+        if (C.dev_setup) fprintf(stderr, "[sx_crossover_band] epoch %d: columns matched to rows at %.1f ms (device, %lld mutual-best rounds)\n", C.epochs, C.ms(), (long long)rounds);
+        else fprintf(stderr, "[sx_crossover_band] epoch %d: columns matched to rows at %.1f ms (host)\n", C.epochs, C.ms());
+    }
+    return SX_OK;
+}
+
+// blocks, the epoch's row maps on the device, band triplets (device set-up: their count and widths; factor_band fills them)
 int epoch_geometry(BandCall &C, const HostLp &lp, const pl::RowPlan &rp, Epoch &E) {
     const int64_t m1_all = static_cast<int64_t>(rp.rows_band.size());
     const int64_t want = getenv("SX_BAND_BLOCKS") ? atoll(getenv("SX_BAND_BLOCKS")) : pl::default_block_count(m1_all);
     pl::make_geometry(lp.csc(), rp, E.mt, want, E.g);
     SX_TRY(E.dev.get(E.g.eqidx.size(), &E.d_eqidx));
     SX_TRY(up(C.s, E.d_eqidx, E.g.eqidx));
-    pl::band_triplets(lp.csc(), lp.nnz, E.g, E.tri);
+    if (!C.dev_setup) {
+        pl::band_triplets(lp.csc(), lp.nnz, E.g, E.tri);
+        E.tri_count = static_cast<int64_t>(E.tri.val.size());
+    } else if (E.g.m1 > 0) {
+        SX_TRY(E.dev.get(E.g.bvar.size(), &E.d_gbvar));
+        SX_TRY(E.dev.get(E.g.rowb.size(), &E.d_growb));
+        SX_TRY(up(C.s, E.d_gbvar, E.g.bvar));
+        SX_TRY(up(C.s, E.d_growb, E.g.rowb));
+        SX_TRY(sx_band_triplets_dev(C.ctx, C.A, E.g.m1, E.d_gbvar, E.d_growb, 0, nullptr, nullptr, nullptr, &E.tri_count, &E.tri.kl, &E.tri.ku));
+    }
     if (!sx_bandlu_supports(E.tri.kl, E.tri.ku)) {
         sx_set_error("the basis is not a band matrix in the order of the rows (kl = %d, ku = %d after setting %lld dense rows aside)", E.tri.kl, E.tri.ku,
                      (long long)E.g.ndr);
         return SX_ERR_UNSUPPORTED;
     }
-    if (C.trace) fprintf(stderr, "[sx_crossover_band] epoch %d: matching and band assembly done at %.1f ms\n", C.epochs, C.ms());
+    if (C.trace) fprintf(stderr, "[sx_crossover_band] epoch %d: matching and band assembly done at %.1f ms (%s)\n", C.epochs, C.ms(), C.dev_setup ? "device" : "host");
     return SX_OK;
 }
 
@@ -1386,13 +1433,17 @@ int factor_band(BandCall &C, Epoch &E, bool guessed) {
         int32_t *d_trow = nullptr, *d_tcol = nullptr;
         double *d_tval = nullptr;
         DevBufs tdev;
-        SX_TRY(tdev.get(E.tri.row.size(), &d_trow));
-        SX_TRY(tdev.get(E.tri.col.size(), &d_tcol));
-        SX_TRY(tdev.get(E.tri.val.size(), &d_tval));
-        SX_TRY(up(s, d_trow, E.tri.row));
-        SX_TRY(up(s, d_tcol, E.tri.col));
-        SX_TRY(up(s, d_tval, E.tri.val));
-        SX_TRY(sx_bandlu_create_dev(C.ctx, m1, E.tri.kl, E.tri.ku, static_cast<int64_t>(E.tri.val.size()), d_trow, d_tcol, d_tval, &E.fac.lu));
+        const size_t nt = static_cast<size_t>(E.tri_count);
+        SX_TRY(tdev.get(nt, &d_trow));
+        SX_TRY(tdev.get(nt, &d_tcol));
+        SX_TRY(tdev.get(nt, &d_tval));
+        if (C.dev_setup) SX_TRY(sx_band_triplets_dev(C.ctx, C.A, m1, E.d_gbvar, E.d_growb, E.tri_count, d_trow, d_tcol, d_tval, nullptr, nullptr, nullptr));
+        else {
+            SX_TRY(up(s, d_trow, E.tri.row));
+            SX_TRY(up(s, d_tcol, E.tri.col));
+            SX_TRY(up(s, d_tval, E.tri.val));
+        }
+        SX_TRY(sx_bandlu_create_dev(C.ctx, m1, E.tri.kl, E.tri.ku, E.tri_count, d_trow, d_tcol, d_tval, &E.fac.lu));
         std::vector<int32_t> rep(static_cast<size_t>(m1)), piv(static_cast<size_t>(m1));
         SX_TRY(sx_bandlu_factor_blocks_dev(E.fac.lu, guessed ? C.tol_band_guess : C.tol_band_keep, static_cast<int>(P), P > 1 ? g.stride : m1, P > 1 ? g.RL : m1,
                                             P > 1 ? g.RL_last : m1, &E.nrep, rep.data(), piv.data()));
@@ -2063,6 +2114,11 @@ int crossover_band_impl(sx_ctx *ctx, const sx_matrix *A, const double *b, const 
     C.opt_tol = opt_tol > 0 ? opt_tol : 1e-7;
     if (getenv("SX_BAND_PIVTOL_B")) C.tol_band_guess = atof(getenv("SX_BAND_PIVTOL_B"));
     if (getenv("SX_BAND_PIVTOL_S")) C.tol_schur_guess = atof(getenv("SX_BAND_PIVTOL_S"));
+    C.dev_setup = ctx->opt_band_setup != 0;
+    if (const char *e = getenv("SX_BAND_SETUP")) {
+        SX_REQUIRE(!strcmp(e, "host") || !strcmp(e, "device"), "SX_BAND_SETUP must be host or device");
+        C.dev_setup = !strcmp(e, "device");
+    }
     *result = sx_simplex_result{};
     result->status = 4;
     // ---- 1. probe shortcut
@@ -2090,8 +2146,7 @@ int crossover_band_impl(sx_ctx *ctx, const sx_matrix *A, const double *b, const 
         const bool guessed = (C.epochs == 1 && !vbasis_in) || C.strict_next;
         C.strict_next = false;
         Epoch E; // this epoch's device arrays and factors
-        pl::match_columns_to_rows(lp.csc(), rp, bs.is_basic, bs.prev_pos, E.mt);
-        if (C.trace) fprintf(stderr, "[sx_crossover_band] epoch %d: columns matched to rows at %.1f ms\n", C.epochs, C.ms());
+        SX_TRY(match_columns(C, lp, rp, bs, E));
         SX_TRY(epoch_geometry(C, lp, rp, E));
         if (probe_only) { // (sx_crossover_band_probe_dev: the matched basis is a band the LU takes -- that was the question)
             result->status = 0;

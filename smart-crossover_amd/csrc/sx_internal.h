@@ -104,6 +104,8 @@ struct sx_ctx {
     int opt_netdual = -1;    // K16d dual network simplex on the whole GPU: -1 / 1 whenever it applies, 0 never
     int opt_nd_grid = 0;     // K16d: workgroups of its cooperative grid (0: by size)
     int opt_spx_pricing = 1; // K16 entering variable: 0 Dantzig (largest reduced cost), 1 Devex reference weights
+    int opt_band_setup = 0;  // K16s: columns matched to band rows and the band assembled by 0 the host (sx_band_plan.h), 1 the
+                             // device (sx_band_match.hip); SX_BAND_SETUP=host|device in the environment overrides it
     int opt_slabs = -1;        // operand slabs of a walk without locality (sx_slabs.h): -1 auto, 0 never, R >= 2: R slabs
     int opt_rb_long_xcd = -1;  // row-blocked walks: the long-row super-tiles dealt over the XCDs (sx_rowblock.h: order[]): -1 when the
                                // matrix puts them unevenly, 0 never, 1 always

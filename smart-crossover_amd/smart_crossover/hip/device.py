@@ -319,6 +319,27 @@ class Context:
         _l.check(rc)
         return True
 
+    def band_match(self, A, is_basic, rowb, m1, prev_pos=None, bvar=None, placed=None):
+        """K16s set-up on the device (blocking): basic columns matched to the ``m1`` band rows, the result of the host's
+        ``sx_plan::match_columns_to_rows``.  Device arrays in; -> (bvar[m1] int64, placed[n + m] uint8, rounds)."""
+        m, n = A.shape
+        bvar = self.empty(m1, np.int64) if bvar is None else bvar
+        placed = self.empty(n + m, np.uint8) if placed is None else placed
+        rounds = C.c_int64(0)
+        _l.check(self._lib.sx_band_match_dev(self.handle, A.handle, _ptr(is_basic), _ptr(rowb), int(m1), _ptr(prev_pos), _ptr(bvar),
+                                             _ptr(placed), C.byref(rounds)))
+        return bvar, placed, int(rounds.value)
+
+    def band_triplets(self, A, bvar, rowb):
+        """K16s set-up on the device (blocking): the band of the matched columns as the device triplets ``BandLU`` takes
+        (-1 / -2 / logical positions: unit vectors) -> (row, col, val, kl, ku)."""
+        cnt, kl, ku = C.c_int64(0), C.c_int(0), C.c_int(0)
+        head = (self.handle, A.handle, int(bvar.size), _ptr(bvar), _ptr(rowb))
+        _l.check(self._lib.sx_band_triplets_dev(*head, 0, None, None, None, C.byref(cnt), C.byref(kl), C.byref(ku)))
+        row, col, val = self.empty(cnt.value, np.int32), self.empty(cnt.value, np.int32), self.empty(cnt.value, np.float64)
+        _l.check(self._lib.sx_band_triplets_dev(*head, cnt.value, row.ptr, col.ptr, val.ptr, C.byref(cnt), C.byref(kl), C.byref(ku)))
+        return row, col, val, int(kl.value), int(ku.value)
+
     def net_simplex(self, A, b, c, l, u, vbasis, cbasis, max_iter=0, feas_tol=1e-7, opt_tol=1e-7, x=None, y=None,
                     vbasis_out=None, cbasis_out=None) -> "_l.SimplexResult":
         """K16n (blocking): primal network simplex from a spanning-tree basis; status 5 = the problem or the
