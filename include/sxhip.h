@@ -659,6 +659,28 @@ int sx_sinkhorn_batch_dev(sx_ctx *ctx, int64_t S, int64_t D, int64_t B, const do
                           const double *M, double reg, int64_t max_iter, double stop_thr, double *plans,
                           double *u_out, double *v_out, sx_sinkhorn_result *results);
 
+/* The same warm start (scripts/run_network_crossover.py:95-97) iterated in the log domain, for a reg so small
+ * that exp(-M/reg) leaves the range of a double and sx_sinkhorn_dev breaks down at once -- e.g. image pairs
+ * restricted to their non-zero pixels (scripts/mnist2ot.py:49-55) with reg of a few thousandths.  Published
+ * algorithm: POT's sinkhorn(..., method='sinkhorn_log'), absent and unpinned -> parity unpinned.  Log-scalings
+ * start at 0; v = log b - LSE_i(-M/reg + u_i), u = log a - LSE_j(-M/reg + v_j); a zero mass takes its point out
+ * (log-scaling -inf, plan entries exactly 0).  Arguments as sx_sinkhorn_dev; outputs (device, any may be NULL):
+ * plan[S*D] = exp(-M/reg + logu_i + logv_j), logu_out[S], logv_out[D].  result->status: 0 iteration limit,
+ * 1 marginal violation < stop_thr, 2 the tested violation is not finite (the pair stays as it is: the log method
+ * has no previous-pair rule).  Blocking. */
+int sx_sinkhorn_log_dev(sx_ctx *ctx, int64_t S, int64_t D, const double *a, const double *b, const double *M,
+                        double reg, int64_t max_iter, double stop_thr, double *plan, double *logu_out,
+                        double *logv_out, sx_sinkhorn_result *result);
+
+/* The log-domain warm start for B <= 16 instance pairs over one cost matrix (the driver's loop over image pairs,
+ * scripts/run_network_crossover.py:95-101; parity unpinned as above): a[B*S], b[B*D] instance-major, mass 0 marks
+ * a grid point an instance does not use.  One load of an element of -M/reg serves four instances; instances stop
+ * independently.  Outputs (device, any may be NULL): plans[B*S*D], logu_out[B*S], logv_out[B*D]; results[B] is
+ * a HOST array.  Blocking. */
+int sx_sinkhorn_log_batch_dev(sx_ctx *ctx, int64_t S, int64_t D, int64_t B, const double *a, const double *b,
+                              const double *M, double reg, int64_t max_iter, double stop_thr, double *plans,
+                              double *logu_out, double *logv_out, sx_sinkhorn_result *results);
+
 /* Session: keeps the basis inverse of the last solve on the device so that the next solve of a
  * column-generation sequence (network_methods/algorithms.py:105-139: same rows, more columns, warm basis
  * = previous optimal basis) starts from it instead of re-installing the basis pivot by pivot.

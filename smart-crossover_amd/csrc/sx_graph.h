@@ -1,4 +1,4 @@
-// A batch of launches with fixed arguments, captured once into a hipGraph and replayed (the five iteration loops of the
+// A batch of launches with fixed arguments, captured once into a hipGraph and replayed (the six iteration loops of the
 // library are launch-bound on small problems).  Direct launches stay each loop's fallback when a batch is not ready().
 #pragma once
 
@@ -36,7 +36,7 @@ struct SxGraphBatch {
     hipError_t launch(hipStream_t s) { return hipGraphLaunch(exec, s); }
 };
 
-// When a loop replays, besides its own size rule: option "graph" (ctx->opt_graph) switches all five off, and each loop
+// When a loop replays, besides its own size rule: option "graph" (ctx->opt_graph) switches all six off, and each loop
 // heeds the environment as it always has --
 //
 //   loop                                  SX_NO_GRAPH set    under a profiler (ROCP_TOOL_LIBRARIES set)
@@ -44,6 +44,7 @@ struct SxGraphBatch {
 //   dense simplex (sx_simplex.hip)        ignored            direct launches
 //   CG (sx_cg.hip)                        direct launches    ignored
 //   Sinkhorn, single and batched          ignored            ignored
+//   log-domain Sinkhorn (both forms)      ignored            ignored
 //
 // SX_NO_GRAPH asks for direct launches (readable traces).  rocprofv3 --kernel-trace (ROCm 7.2) faults inside
 // hipGraphLaunch after some thousands of replays: profiles/r03/hipgraph_rocprofv3.md, the frames are named in

@@ -93,7 +93,7 @@ struct sx_ctx {
     int opt_xcd_swizzle = 1; // XCD-contiguous block -> tile map
     int opt_window = -1;     // LDS operand window of the column walk: -1 auto, 0 off, 1/2/4/8 tiles per load
     int opt_graph = 1;       // replay iteration batches as hipGraphs: CG, first-order LP stage (K16p), dense simplex (K16) and
-                             // both Sinkhorns; 0: direct launches in all five (sx_graph.h holds what else each loop heeds)
+                             // the Sinkhorns, plain and log-domain; 0: direct launches in all six (sx_graph.h holds what else each loop heeds)
     int opt_spx_defer = -1;  // K16 basis inverse: -1 auto, 0 rank-one update per pivot, 1 rank-32 update per batch
     int opt_rowblock = -1;   // column-blocked row layout of the row walk: -1 auto, 0 off, 1 whenever possible
     int opt_spx_check = 2048; // K16: pivots between two checks of A x + s = b (drift of the explicit inverse)

@@ -6,6 +6,10 @@ module offers the same call -- same argument names and defaults as ``ot.sinkhorn
 reference uses -- computed by ``sx_sinkhorn_dev`` (csrc/sx_sinkhorn.hip).  POT is a third-party package
 that is neither vendored nor pinned by the reference, so parity is unpinned; the tests compare with a
 restatement of POT's published ``sinkhorn_knopp`` (oracle/sinkhorn.py).
+
+``method="sinkhorn_log"`` runs POT's log-domain iteration instead (``sx_sinkhorn_log_dev``,
+csrc/sx_sinkhorn_log.hip): the same plan in exact arithmetic, and still a plan when ``reg`` is so small that
+``exp(-M/reg)`` underflows and the default method stops at iteration 0 with a warning.
 """
 from __future__ import annotations
 
@@ -15,10 +19,22 @@ from typing import Tuple, Union
 import numpy as np
 
 
+METHODS = ("sinkhorn", "sinkhorn_log")
+
+
+def _log_dict(log_u: np.ndarray, log_v: np.ndarray, res) -> dict:
+    with np.errstate(over="ignore"):             # a log-scaling above 709 has no double: inf, as POT reports it
+        return {"log_u": log_u, "log_v": log_v, "u": np.exp(log_u), "v": np.exp(log_v), "niter": int(res.iters),
+                "err": float(res.err)}
+
+
 def sinkhorn(a: np.ndarray, b: np.ndarray, M: np.ndarray, reg: float, numItermax: int = 1000, stopThr: float = 1e-9,
-             log: bool = False) -> Union[np.ndarray, Tuple[np.ndarray, dict]]:
+             log: bool = False, method: str = "sinkhorn") -> Union[np.ndarray, Tuple[np.ndarray, dict]]:
     """Sinkhorn-Knopp plan ``diag(u) exp(-M/reg) diag(v)`` for marginals ``a`` (sources) and ``b``
-    (targets); with ``log=True`` also a dict with ``u``, ``v``, ``niter`` and the last tested ``err``."""
+    (targets); with ``log=True`` also a dict with ``u``, ``v``, ``niter`` and the last tested ``err``.
+    ``method="sinkhorn_log"`` iterates on the log-scalings (any ``reg > 0``); its dict also has ``log_u``, ``log_v``."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     from smart_crossover.hip.device import default_context
     a = np.ascontiguousarray(a, dtype=np.float64)
     b = np.ascontiguousarray(b, dtype=np.float64)
@@ -28,6 +44,13 @@ def sinkhorn(a: np.ndarray, b: np.ndarray, M: np.ndarray, reg: float, numItermax
     ctx = default_context()
     S, D = M.shape
     plan, u, v = ctx.empty(S * D, np.float64), ctx.empty(S, np.float64), ctx.empty(D, np.float64)
+    if method == "sinkhorn_log":
+        res = ctx.sinkhorn_log(S, D, ctx.to_device(a), ctx.to_device(b), ctx.to_device(M.reshape(-1)), reg, numItermax,
+                               stopThr, plan, u, v)
+        if res.status == 2:
+            warnings.warn(f"Warning: numerical errors at iteration {int(res.iters)}")
+        out = plan.download().reshape(S, D)
+        return (out, _log_dict(u.download(), v.download(), res)) if log else out
     res = ctx.sinkhorn(S, D, ctx.to_device(a), ctx.to_device(b), ctx.to_device(M.reshape(-1)), reg, numItermax, stopThr,
                        plan, u, v)
     if res.status == 2:
@@ -39,13 +62,17 @@ def sinkhorn(a: np.ndarray, b: np.ndarray, M: np.ndarray, reg: float, numItermax
 
 
 def sinkhorn_batch(a: np.ndarray, b: np.ndarray, M: np.ndarray, reg: float, numItermax: int = 1000,
-                   stopThr: float = 1e-9, log: bool = False):
+                   stopThr: float = 1e-9, log: bool = False, method: str = "sinkhorn"):
     """The warm starts of several instance pairs that share one cost matrix -- the reference's driver loops over
     ten MNIST image pairs on the same pixel grid (scripts/run_network_crossover.py:95-101) -- in one go:
     ``a`` is (B, S), ``b`` is (B, D), ``M`` is (S, D); a grid point an instance does not use carries mass 0 and
     drops out of that instance exactly as if it had been removed from its support.  Returns the (B, S, D) plans;
     with ``log=True`` also a list of dicts (``u``, ``v``, ``niter``, ``err``) per instance.  Batches of up to 16
-    instances run as dense products on the fp64 matrix cores (``sx_sinkhorn_batch_dev``)."""
+    instances run as dense products on the fp64 matrix cores (``sx_sinkhorn_batch_dev``);
+    ``method="sinkhorn_log"`` runs them through the log-domain kernels (``sx_sinkhorn_log_batch_dev``), where an
+    unused grid point has log-scaling ``-inf``."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     from smart_crossover.hip.device import default_context
     a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
     b = np.ascontiguousarray(np.atleast_2d(b), dtype=np.float64)
@@ -61,12 +88,14 @@ def sinkhorn_batch(a: np.ndarray, b: np.ndarray, M: np.ndarray, reg: float, numI
     for lo in range(0, B, 16):
         nb = min(16, B - lo)
         d_plan, d_u, d_v = ctx.empty(nb * S * D, np.float64), ctx.empty(nb * S, np.float64), ctx.empty(nb * D, np.float64)
-        res = ctx.sinkhorn_batch(S, D, nb, ctx.to_device(a[lo:lo + nb].reshape(-1)), ctx.to_device(b[lo:lo + nb].reshape(-1)),
-                                 dM, reg, numItermax, stopThr, d_plan, d_u, d_v)
+        run = ctx.sinkhorn_log_batch if method == "sinkhorn_log" else ctx.sinkhorn_batch
+        res = run(S, D, nb, ctx.to_device(a[lo:lo + nb].reshape(-1)), ctx.to_device(b[lo:lo + nb].reshape(-1)),
+                  dM, reg, numItermax, stopThr, d_plan, d_u, d_v)
         plans[lo:lo + nb] = d_plan.download().reshape(nb, S, D)
         u, v = d_u.download().reshape(nb, S), d_v.download().reshape(nb, D)
         for k, r in enumerate(res):
             if r.status == 2:
                 warnings.warn(f"Warning: numerical errors at iteration {int(r.iters)} (instance {lo + k})")
-            logs.append({"u": u[k], "v": v[k], "niter": int(r.iters), "err": float(r.err)})
+            logs.append(_log_dict(u[k], v[k], r) if method == "sinkhorn_log" else
+                        {"u": u[k], "v": v[k], "niter": int(r.iters), "err": float(r.err)})
     return (plans, logs) if log else plans
