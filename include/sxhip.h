@@ -681,6 +681,20 @@ int sx_sinkhorn_log_batch_dev(sx_ctx *ctx, int64_t S, int64_t D, int64_t B, cons
                               const double *M, double reg, int64_t max_iter, double stop_thr, double *plans,
                               double *logu_out, double *logv_out, sx_sinkhorn_result *results);
 
+/* The log-domain warm start for B >= 1 image pairs on an H x W pixel grid whose cost is separable: the reference
+ * builds M[(y,x),(y',x')] = |y - y'| + |x - x'| (scripts/mnist2ot.py:30-40) and its driver solves ten such pairs
+ * (scripts/run_network_crossover.py:95-101; POT absent and unpinned -> parity unpinned).  Here M = Cy[y,y'] + Cx[x,x']
+ * with Cy[H*H] and Cx[W*W] holding any values (row-major, device), so squared distances work as well as |d|.  The
+ * algorithm is that of sx_sinkhorn_log_dev; every log-sum-exp is taken along x, then along y, and one workgroup
+ * iterates one pair entirely in LDS: no n x n array exists until the plans are written, and B has no cap.
+ * a[B*H*W], b[B*H*W] instance-major, row-major over the grid; mass 0 takes a pixel out of its instance (log-scaling
+ * -inf, plan entries exactly 0).  Outputs (device, any may be NULL): plans[B*n*n] with n = H*W, logu_out[B*n],
+ * logv_out[B*n]; results[B] is a HOST array, status as sx_sinkhorn_log_dev.  A grid whose working set does not fit
+ * one CU's LDS -- W*(W|1) + H*(H|1) + 4*H*W > 20,000 doubles; 56 x 56 fits -- returns SX_ERR_UNSUPPORTED.  Blocking. */
+int sx_sinkhorn_grid_dev(sx_ctx *ctx, int64_t H, int64_t W, int64_t B, const double *a, const double *b,
+                         const double *Cy, const double *Cx, double reg, int64_t max_iter, double stop_thr,
+                         double *plans, double *logu_out, double *logv_out, sx_sinkhorn_result *results);
+
 /* Session: keeps the basis inverse of the last solve on the device so that the next solve of a
  * column-generation sequence (network_methods/algorithms.py:105-139: same rows, more columns, warm basis
  * = previous optimal basis) starts from it instead of re-installing the basis pivot by pivot.

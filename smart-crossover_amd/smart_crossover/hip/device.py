@@ -391,6 +391,15 @@ class Context:
                                                      int(max_iter), float(stop_thr), _ptr(plans), _ptr(log_u), _ptr(log_v), res))
         return list(res)
 
+    def sinkhorn_grid(self, H, W, B, a, b, Cy, Cx, reg, max_iter=1000, stop_thr=1e-9, plans=None, log_u=None, log_v=None):
+        """B >= 1 log-domain warm starts on an H x W grid with the separable cost Cy[y,y'] + Cx[x,x'] (blocking), one
+        workgroup per instance; returns the B result records.  NotImplementedError when the grid does not fit the LDS."""
+        res = (_l.SinkhornResult * int(B))()
+        _l.check(self._lib.sx_sinkhorn_grid_dev(self.handle, int(H), int(W), int(B), _ptr(a), _ptr(b), _ptr(Cy), _ptr(Cx),
+                                                float(reg), int(max_iter), float(stop_thr), _ptr(plans), _ptr(log_u),
+                                                _ptr(log_v), res))
+        return list(res)
+
     def x_real(self, n, x, l, u, out, apply_floor: bool = True) -> None:
         _l.check(self._lib.sx_x_real_dev(self.handle, int(n), _ptr(x), _ptr(l), _ptr(u), int(bool(apply_floor)),
                                          _ptr(out)))

@@ -10,6 +10,9 @@ restatement of POT's published ``sinkhorn_knopp`` (oracle/sinkhorn.py).
 ``method="sinkhorn_log"`` runs POT's log-domain iteration instead (``sx_sinkhorn_log_dev``,
 csrc/sx_sinkhorn_log.hip): the same plan in exact arithmetic, and still a plan when ``reg`` is so small that
 ``exp(-M/reg)`` underflows and the default method stops at iteration 0 with a warning.
+
+``sinkhorn_grid`` runs the same log-domain iteration for image pairs on a pixel grid with a separable cost
+(``sx_sinkhorn_grid_dev``, csrc/sx_sinkhorn_grid.hip): no dense ``M``, any number of pairs per call.
 """
 from __future__ import annotations
 
@@ -98,4 +101,70 @@ def sinkhorn_batch(a: np.ndarray, b: np.ndarray, M: np.ndarray, reg: float, numI
                 warnings.warn(f"Warning: numerical errors at iteration {int(r.iters)} (instance {lo + k})")
             logs.append(_log_dict(u[k], v[k], r) if method == "sinkhorn_log" else
                         {"u": u[k], "v": v[k], "niter": int(r.iters), "err": float(r.err)})
+    return (plans, logs) if log else plans
+
+
+GRID_PLAN_BYTES = 1 << 30        # device plan buffer of one sinkhorn_grid call: larger batches are cut into several
+
+
+def _axis_costs(shape, cost):
+    H, W = shape
+    if isinstance(cost, str):
+        if cost not in ("cityblock", "sqeuclidean"):
+            raise ValueError(f"cost must be 'cityblock', 'sqeuclidean' or a pair (Cy, Cx), not {cost!r}")
+        power = 1 if cost == "cityblock" else 2
+        return tuple(np.abs(np.subtract.outer(np.arange(k), np.arange(k))).astype(np.float64) ** power for k in (H, W))
+    try:
+        Cy, Cx = (np.ascontiguousarray(c, dtype=np.float64) for c in cost)
+    except (TypeError, ValueError):
+        raise ValueError("cost must be 'cityblock', 'sqeuclidean' or a pair (Cy, Cx)") from None
+    if Cy.shape != (H, H) or Cx.shape != (W, W):
+        raise ValueError("Cy must be (H, H) and Cx (W, W)")
+    return Cy, Cx
+
+
+def sinkhorn_grid(a: np.ndarray, b: np.ndarray, shape: Tuple[int, int], reg: float, numItermax: int = 1000,
+                  stopThr: float = 1e-9, log: bool = False, cost="cityblock"):
+    """Log-domain warm starts of image pairs on an ``H x W`` pixel grid whose cost is separable,
+    ``M[(y,x),(y',x')] = Cy[y,y'] + Cx[x,x']`` -- the ``|dy| + |dx|`` of scripts/mnist2ot.py:30-40 (``"cityblock"``),
+    squared distances (``"sqeuclidean"``) or any pair ``(Cy, Cx)`` -- without ever building ``M``: one workgroup
+    iterates one pair in LDS (``sx_sinkhorn_grid_dev``, csrc/sx_sinkhorn_grid.hip), any number of pairs per call.
+    ``a`` and ``b`` are ``(H*W,)`` or ``(B, H*W)``, row-major over the grid, mass 0 = pixel not used.  Returns what
+    ``sinkhorn(..., method="sinkhorn_log")`` / ``sinkhorn_batch(..., method="sinkhorn_log")`` return for the dense
+    ``M``.  Batches are cut so that the device plan buffer stays within ``GRID_PLAN_BYTES`` (1 GiB).  A grid beyond
+    the kernel's limit (``W*(W|1) + H*(H|1) + 4*H*W <= 20000``; 56 x 56 fits) raises ``ValueError``."""
+    from smart_crossover.hip.device import default_context
+    try:
+        H, W = (int(k) for k in shape)
+    except (TypeError, ValueError):
+        raise ValueError("shape must be (H, W)") from None
+    single = np.ndim(a) == 1
+    a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
+    b = np.ascontiguousarray(np.atleast_2d(b), dtype=np.float64)
+    n = H * W
+    if H < 1 or W < 1 or a.ndim != 2 or a.shape[1] != n or b.shape != a.shape:
+        raise ValueError("a and b must be (H*W,) or (B, H*W) for shape = (H, W)")
+    Cy, Cx = _axis_costs((H, W), cost)
+    ctx = default_context()
+    dCy, dCx = ctx.to_device(Cy.reshape(-1)), ctx.to_device(Cx.reshape(-1))
+    B = a.shape[0]
+    chunk = max(1, min(B, GRID_PLAN_BYTES // (8 * n * n)))
+    plans = np.empty((B, n, n))
+    logs = []
+    for lo in range(0, B, chunk):
+        nb = min(chunk, B - lo)
+        d_plan, d_u, d_v = ctx.empty(nb * n * n, np.float64), ctx.empty(nb * n, np.float64), ctx.empty(nb * n, np.float64)
+        try:
+            res = ctx.sinkhorn_grid(H, W, nb, ctx.to_device(a[lo:lo + nb].reshape(-1)), ctx.to_device(b[lo:lo + nb].reshape(-1)),
+                                    dCy, dCx, reg, numItermax, stopThr, d_plan, d_u, d_v)
+        except NotImplementedError as exc:       # SX_ERR_UNSUPPORTED: the grid does not fit the LDS of one CU
+            raise ValueError(str(exc)) from None
+        plans[lo:lo + nb] = d_plan.download().reshape(nb, n, n)
+        u, v = d_u.download().reshape(nb, n), d_v.download().reshape(nb, n)
+        for k, r in enumerate(res):
+            if r.status == 2:
+                warnings.warn(f"Warning: numerical errors at iteration {int(r.iters)}" + ("" if single else f" (instance {lo + k})"))
+            logs.append(_log_dict(u[k], v[k], r))
+    if single:
+        return (plans[0], logs[0]) if log else plans[0]
     return (plans, logs) if log else plans

@@ -2,7 +2,8 @@
 """What a sharper entropic plan is worth to the OT crossover: on the side x side grid (28 = BASELINE config 3 size)
 one instance pair, its warm start by each Sinkhorn method at several reg, and TNET from each plan -- iterations
 (pushes + simplex) and wall time of network_crossover, objective against the first finished run.
-    python tools/sinkhorn_crossover.py [--side 28] [--regs 10 1 0.1 0.02 0.005] [--iters 1000]
+    python tools/sinkhorn_crossover.py [--side 28] [--regs 10 1 0.1 0.02 0.005] [--iters 1000] [--methods sinkhorn sinkhorn_log]
+--methods may name sinkhorn_grid (the separable-grid kernel, any iteration count at a usable cost).
 """
 import argparse
 import io
@@ -27,10 +28,11 @@ def main():
     ap.add_argument("--side", type=int, default=28)
     ap.add_argument("--regs", type=float, nargs="+", default=[10.0, 1.0, 0.1, 0.02, 0.005])
     ap.add_argument("--iters", type=int, default=1000)
+    ap.add_argument("--methods", nargs="+", default=["sinkhorn", "sinkhorn_log"], choices=("sinkhorn", "sinkhorn_log", "sinkhorn_grid"))
     args = ap.parse_args()
     from smart_crossover.formats import OptTransport
     from smart_crossover.network_methods.algorithms import network_crossover
-    from smart_crossover.sinkhorn import sinkhorn
+    from smart_crossover.sinkhorn import sinkhorn, sinkhorn_grid
     from smart_crossover.solver_caller.caller import SolverSettings
     n = args.side * args.side
     rng = np.random.default_rng(3)
@@ -49,11 +51,14 @@ def main():
     rows = []
     warm = False
     for reg in args.regs:
-        for method in ("sinkhorn", "sinkhorn_log"):
+        for method in args.methods:
             t0 = time.perf_counter()
             with warnings.catch_warnings(record=True) as caught:
                 warnings.simplefilter("always")
-                plan, log = sinkhorn(a, b, M, reg, numItermax=args.iters, log=True, method=method)
+                if method == "sinkhorn_grid":
+                    plan, log = sinkhorn_grid(a, b, (args.side, args.side), reg, numItermax=args.iters, log=True)
+                else:
+                    plan, log = sinkhorn(a, b, M, reg, numItermax=args.iters, log=True, method=method)
             row = {"reg": reg, "method": method, "sinkhorn_s": time.perf_counter() - t0, "niter": log["niter"],
                    "err": log["err"], "broke_down": any("numerical errors" in str(w.message) for w in caught), "plan_nonzeros": int(np.count_nonzero(plan))}
             try:
