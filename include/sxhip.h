@@ -64,7 +64,11 @@ int sx_ctx_sync(sx_ctx *ctx);
 /* Tuning knobs (performance only; the kernels of the scoring / pricing / CG path return identical bits
  * under every setting, the simplex the same optimum up to rounding): "xcd_swizzle" 0/1 (default 1),
  * "window" (LDS operand window of the column walk in K1/K10: -1 auto [default: decided per matrix from its index clustering on first use],
- * 0 off, 1/2/4/8 tiles per window load), "graph" 0/1 (default 1: hipGraph replay of the CG iteration batch),
+ * 0 off, 1/2/4/8 tiles per window load), "lanes" (lane-major copy of the columns for the windowed walk of K1/K10,
+ * csrc/sx_lanes.h: built when the window is in use and the matrix is eligible -- no column of a tile longer than 64
+ * entries, padded slots at most 9/8 of the entries -- 1 by the first K1 / K10 call or query, -1 auto [default] by the second
+ * K1 / K10 call on the matrix, so that a matrix scored once pays nothing, 0 off; bit-identical either way, about 12 bytes
+ * of device memory per entry), "graph" 0/1 (default 1: hipGraph replay of the CG iteration batch),
  * "rb_stage_long" (in the column-blocked row layout the products of the long rows -- the linking rows of an LP -- come
  * from a column-ordered pre-pass, which sorts them in LDS into the layout's order and writes them in whole lines, instead
  * of one gathered 128-byte line of x per entry: -1 auto [default: layouts with at least 2^21 long entries], 0 never,
@@ -174,6 +178,10 @@ int sx_matrix_rowblock_long_download(sx_ctx *ctx, const sx_matrix *A, int32_t *l
  * is the plain one.  For tests, tools and bench.py; the walks (sx_score_columns_dev / sx_score_rows_dev /
  * sx_price_dev, reference formats.py:70-76, net_manager.py:302-303) pick the slabs up by themselves. */
 int sx_matrix_slabs_info(sx_ctx *ctx, const sx_matrix *A, int which, int64_t *info);
+/* Lane-major copy of A's columns under the context's "window" and "lanes" options (built now if it is due;
+ * csrc/sx_lanes.h): info[0..2] = tiles, slots including padding, bytes of device memory; all zero when the next K1 /
+ * K10 call uses the staged walk on this matrix. */
+int sx_matrix_lanes_info(sx_ctx *ctx, const sx_matrix *A, int64_t *info);
 
 /* ------------------------------------------------------------------ K1: column scoring
  * replaces GeneralLP.get_dual_slack (formats.py:70-72) and the two np.where tests of

@@ -2,6 +2,7 @@
 #include "sx_internal.h"
 #include "sx_rowblock.h"
 #include "sx_slabs.h"
+#include "sx_lanes.h"
 
 #include <algorithm>
 
@@ -165,6 +166,9 @@ SX_API int sx_ctx_set_option(sx_ctx *ctx, const char *key, int64_t value) {
         ctx->opt_xcd_swizzle = value ? 1 : 0;
     } else if (!strcmp(key, "window")) {
         ctx->opt_window = value < 0 ? -1 : static_cast<int>(value);
+    } else if (!strcmp(key, "lanes")) {
+        SX_REQUIRE(value >= -1 && value <= 1, "lanes must be -1 (auto), 0 (off) or 1 (whenever the matrix is eligible)");
+        ctx->opt_lanes = static_cast<int>(value);
     } else if (!strcmp(key, "netsimplex")) {
         SX_REQUIRE(value >= -1 && value <= 1, "netsimplex must be -1 (by size), 0 (off) or 1 (whenever it applies)");
         ctx->opt_netsimplex = static_cast<int>(value);
@@ -559,6 +563,7 @@ SX_API int sx_matrix_destroy(sx_matrix *A) {
     for (void *p : ptrs)
         if (p) (void)sx_dfree(p);
     sx_rowblock_free(A->rb);
+    sx_lanes_free(A->lanes);
     sx_slabs_free(A->slabs[0]);
     sx_slabs_free(A->slabs[1]);
     delete A;

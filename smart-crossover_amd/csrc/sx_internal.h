@@ -92,6 +92,7 @@ struct sx_ctx {
     // tuning knobs (sx_ctx_set_option); defaults are the measured best on MI355X
     int opt_xcd_swizzle = 1; // XCD-contiguous block -> tile map
     int opt_window = -1;     // LDS operand window of the column walk: -1 auto, 0 off, 1/2/4/8 tiles per load
+    int opt_lanes = -1;      // lane-major tile slabs of the windowed column walk (sx_lanes.h): -1 from a matrix' second walk on, 1 at once, 0 never
     int opt_graph = 1;       // replay iteration batches as hipGraphs: CG, first-order LP stage (K16p), dense simplex (K16) and
                              // the Sinkhorns, plain and log-domain; 0: direct launches in all six (sx_graph.h holds what else each loop heeds)
     int opt_spx_defer = -1;  // K16 basis inverse: -1 auto, 0 rank-one update per pivot, 1 rank-32 update per batch
@@ -199,6 +200,10 @@ struct sx_matrix {
     mutable int csc_win_tuned = 0;
     mutable int csc_swizzle_off = 0; // window_autotune: this matrix' column walk is faster WITHOUT the XCD-contiguous tile map
     mutable int csc_win_local = 0;  // at least half of a tile's sampled indices inside one 4096-row window: the gathers have locality
+    // optional lane-major copy of the columns for the windowed column walk (sx_lanes.h), built on first use
+    mutable struct sx_lanes *lanes = nullptr;
+    mutable int lanes_tried = 0;
+    mutable int lanes_asked = 0; // a K1 / K10 call has wanted the copy before (the automatic rule builds it for the second)
     // optional column-blocked copy of the rows (sx_rowblock.h), built on first use of a row walk
     mutable struct sx_rowblock *rb = nullptr;
     mutable int rb_tried = 0; // 1: the automatic rule has spoken, 2: so has a forced build

@@ -6,6 +6,7 @@
 #include "sx_rowblock.h"
 #include "sx_segwalk.h"
 #include "sx_window.h"
+#include "sx_lanes.h"
 #include "sx_slabs.h"
 
 #include <cmath>
@@ -110,6 +111,21 @@ __global__ __launch_bounds__(SX_WG) void k_score_columns_lw(
     if (run >= nruns) return;
     ScoreColumnsEpilogue epi{c, x, l, u, gamma, s_d, code};
     sx_window_walk<RUN>(tiles, ntiles, run, win_lo, colptr, rowidx, val, y, m, lds, win, false, epi);
+}
+
+// K1 over the lane-major slabs (sx_lanes.h): the same runs behind a window of SXN_CAP rows, the sums formed in registers
+template <int RUN>
+__global__ __launch_bounds__(SX_WG) void k_score_columns_ln(
+    const int64_t *__restrict__ tiles, int64_t ntiles, int swizzle, const int32_t *__restrict__ win_lo,
+    const uint8_t *__restrict__ slab, const int64_t *__restrict__ off, int64_t m, const double *__restrict__ y,
+    const double *__restrict__ c, const double *__restrict__ x, const double *__restrict__ l,
+    const double *__restrict__ u, double gamma, double *__restrict__ s_d, uint8_t *__restrict__ code) {
+    __shared__ double win[SXN_CAP];
+    const int64_t nruns = (ntiles + RUN - 1) / RUN;
+    const int64_t run = sx_tile_of_block(blockIdx.x, nruns, swizzle);
+    if (run >= nruns) return;
+    ScoreColumnsEpilogue epi{c, x, l, u, gamma, s_d, code};
+    sx_lanes_walk<RUN>(tiles, ntiles, run, win_lo, slab, off, y, m, win, false, epi);
 }
 
 // ------------------------------------------------------------------------------------- K2
@@ -260,6 +276,22 @@ __global__ __launch_bounds__(SX_WG, 4) void k_price_lw(
     for (; r < r_end; r += r_step) sx_window_walk<RUN>(tiles, ntiles, r, win_lo, colptr, rowidx, val, y, m, lds, win, true, epi);
     __syncthreads(); // the last tile's sums are out of the product buffer
     price_block_reduce(epi.v, epi.ix, epi.bad, &partial[blockIdx.x], lds.v[0]);
+}
+
+// K10 over the lane-major slabs (sx_lanes.h); the reduction borrows the window once the last run is done with it
+template <int RUN>
+__global__ __launch_bounds__(SX_WG) void k_price_ln(
+    const int64_t *__restrict__ tiles, int64_t ntiles, int swizzle, const int32_t *__restrict__ win_lo,
+    const uint8_t *__restrict__ slab, const int64_t *__restrict__ off, int64_t m, const double *__restrict__ y,
+    const double *__restrict__ c, const int8_t *__restrict__ vbasis, double tol, double *__restrict__ rc_out,
+    PricePartial *__restrict__ partial) {
+    __shared__ double win[SXN_CAP];
+    PriceEpilogue epi{c, vbasis, tol, rc_out};
+    int64_t r, r_end, r_step;
+    sx_walk_range((ntiles + RUN - 1) / RUN, swizzle, r, r_end, r_step);
+    for (; r < r_end; r += r_step) sx_lanes_walk<RUN>(tiles, ntiles, r, win_lo, slab, off, y, m, win, true, epi);
+    __syncthreads(); // the last run's gathers are done with the window
+    price_block_reduce(epi.v, epi.ix, epi.bad, &partial[blockIdx.x], win);
 }
 
 __global__ __launch_bounds__(SX_WG) void k_price_final(const PricePartial *__restrict__ partial,
@@ -475,23 +507,34 @@ static int slab_passes(sx_ctx *ctx, const sx_slabs *S, const double *operand) {
     return SX_OK;
 }
 
-// K1 behind the window, `run` tiles per window load
-static void launch_score_columns_lw(sx_ctx *ctx, const sx_matrix *A, int run, int swz, const double *y, const double *c,
+// K1 behind the window, `run` tiles per window load; S: the matrix' lane-major slabs (sx_lanes.h), nullptr: staged walk
+static void launch_score_columns_lw(sx_ctx *ctx, const sx_matrix *A, const sx_lanes *S, int run, int swz, const double *y, const double *c,
                                     const double *x, const double *l, const double *u, double gamma, double *s_d,
                                     uint8_t *code) {
     sx_window_with_run<8, 4, 2, 1>(run, [&](auto R) {
         constexpr int RUN = decltype(R)::value;
         const int64_t nruns = (A->n_csc_tiles + RUN - 1) / RUN;
+        if (S) {
+            hipLaunchKernelGGL(k_score_columns_ln<RUN>, dim3(walk_grid(ctx, nruns)), dim3(SX_WG), 0, ctx->stream,
+                               A->csc_tiles, A->n_csc_tiles, swz, A->csc_win_lo, S->slab, S->off, A->m, y, c, x, l, u,
+                               gamma, s_d, code);
+            return;
+        }
         hipLaunchKernelGGL(k_score_columns_lw<RUN>, dim3(walk_grid(ctx, nruns)), dim3(SX_WG), 0, ctx->stream,
                            A->csc_tiles, A->n_csc_tiles, swz, A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, A->m, y,
                            c, x, l, u, gamma, s_d, code);
     });
 }
 
-// K10 behind the window, `run` tiles per window load, on nb workgroups
-static void launch_price_lw(sx_ctx *ctx, const sx_matrix *A, int run, int swz, int nb, const double *y, const double *c,
+// K10 behind the window, `run` tiles per window load, on nb workgroups; S as above
+static void launch_price_lw(sx_ctx *ctx, const sx_matrix *A, const sx_lanes *S, int run, int swz, int nb, const double *y, const double *c,
                             const int8_t *vbasis, double tol, double *rc, PricePartial *partial) {
     sx_window_with_run<8, 4, 2, 1>(run, [&](auto R) {
+        if (S) {
+            hipLaunchKernelGGL(k_price_ln<decltype(R)::value>, dim3(nb), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles,
+                               swz, A->csc_win_lo, S->slab, S->off, A->m, y, c, vbasis, tol, rc, partial);
+            return;
+        }
         hipLaunchKernelGGL(k_price_lw<decltype(R)::value>, dim3(nb), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles, swz,
                            A->csc_win_lo, A->csc_ptr, A->csc_idx, A->csc_val, A->m, y, c, vbasis, tol, rc, partial);
     });
@@ -575,7 +618,7 @@ SX_API int sx_score_columns_dev(sx_ctx *ctx, const sx_matrix *A, const double *y
     int run = 0; // LDS operand window (sx_window.h): table built on first use; a large matrix is timed once, else the rule decides
     SX_TRY(window_autotune(ctx, A, [&](int windowed, int swz) -> int {
         if (windowed) {
-            launch_score_columns_lw(ctx, A, 4, swz, y, c, x, l, u, gamma, s_d, code);
+            launch_score_columns_lw(ctx, A, nullptr, 4, swz, y, c, x, l, u, gamma, s_d, code);
         } else {
             hipLaunchKernelGGL(k_score_columns<0>, dim3(walk_grid(ctx, A->n_csc_tiles)), dim3(SX_WG), 0, ctx->stream, A->csc_tiles,
                                A->n_csc_tiles, swz, A->csc_ptr, A->csc_idx, A->csc_val, y, c, x, l, u, gamma, s_d, code,
@@ -585,7 +628,9 @@ SX_API int sx_score_columns_dev(sx_ctx *ctx, const sx_matrix *A, const double *y
     }));
     SX_TRY(sx_window_run_csc(ctx, A, &run));
     if (run) {
-        launch_score_columns_lw(ctx, A, run, sx_csc_swizzle(ctx, A), y, c, x, l, u, gamma, s_d, code);
+        const sx_lanes *S = nullptr;
+        SX_TRY(sx_lanes_get(ctx, A, true, &S));
+        launch_score_columns_lw(ctx, A, S, run, sx_csc_swizzle(ctx, A), y, c, x, l, u, gamma, s_d, code);
         SX_HIP(hipGetLastError());
         return SX_OK;
     }
@@ -720,7 +765,7 @@ SX_API int sx_price_dev(sx_ctx *ctx, const sx_matrix *A, const double *y, const 
     SX_TRY(window_autotune(ctx, A, [&](int windowed, int swz_) -> int {
         return price_launch(ctx, A->n_csc_tiles, 1, nullptr, [&](int nb, PricePartial *partial) {
             if (windowed)
-                launch_price_lw(ctx, A, 4, swz_, nb, y, c, vbasis, tol, rc, partial);
+                launch_price_lw(ctx, A, nullptr, 4, swz_, nb, y, c, vbasis, tol, rc, partial);
             else
                 hipLaunchKernelGGL(k_price<0>, dim3(nb), dim3(SX_WG), 0, ctx->stream, A->csc_tiles, A->n_csc_tiles, swz_, A->csc_ptr,
                                    A->csc_idx, A->csc_val, y, c, vbasis, tol, rc, partial, static_cast<const double *>(nullptr));
@@ -735,10 +780,13 @@ SX_API int sx_price_dev(sx_ctx *ctx, const sx_matrix *A, const double *y, const 
     const int swz = sx_csc_swizzle(ctx, A);
     int run = 0;
     SX_TRY(sx_window_run_csc(ctx, A, &run));
-    if (run)
+    if (run) {
+        const sx_lanes *S = nullptr; // (built here, ahead of price_launch: the build's scan uses the workspace too)
+        SX_TRY(sx_lanes_get(ctx, A, true, &S));
         return price_launch(ctx, A->n_csc_tiles, swz, result_dev, [&](int nb, PricePartial *partial) {
-            launch_price_lw(ctx, A, run, swz, nb, y, c, vbasis, tol, rc, partial);
+            launch_price_lw(ctx, A, S, run, swz, nb, y, c, vbasis, tol, rc, partial);
         });
+    }
     {   // no locality and an operand beyond L2: slab after slab (sx_slabs.h), pricing in the last pass
         const sx_slabs *S = nullptr;
         SX_TRY(sx_slabs_get(ctx, A, 1, &S));

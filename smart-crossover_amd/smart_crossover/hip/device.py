@@ -581,6 +581,14 @@ class DeviceMatrix:
         _l.check(self.ctx._lib.sx_matrix_slabs_info(self.ctx.handle, self.handle, int(which), info))
         return None if info[0] == 0 else dict(R=int(info[0]), width=int(info[1]), nseg=int(info[2]))
 
+    def lanes(self):
+        """Lane-major copy of the columns (csrc/sx_lanes.h) under the context's "window" and "lanes" options, built now
+        if due (option -1: once K1 or K10 has walked the matrix): dict(tiles, slots, bytes), or None when the next K1 / K10
+        call uses the staged walk on this matrix."""
+        info = (C.c_int64 * 3)()
+        _l.check(self.ctx._lib.sx_matrix_lanes_info(self.ctx.handle, self.handle, info))
+        return None if info[0] == 0 else dict(tiles=int(info[0]), slots=int(info[1]), bytes=int(info[2]))
+
     def rowblock(self, download: bool = False):
         """Column-blocked row layout of the matrix (csrc/sx_rowblock.h) under the context's "rowblock"
         option, built now if due: a dict with the counts and, with ``download``, the arrays; None when the

@@ -102,6 +102,7 @@ PROTOTYPES = {
     "sx_matrix_download_csr": (_int, [_vp, _vp, _vp, _vp]),
     "sx_matrix_rowblock_info": (_int, [_vp, _vp, _vp]),
     "sx_matrix_slabs_info": (_int, [_vp, _vp, _int, _vp]),
+    "sx_matrix_lanes_info": (_int, [_vp, _vp, _vp]),
     "sx_matrix_rowblock_download": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sx_matrix_rowblock_long_info": (_int, [_vp, _vp, _vp]),
     "sx_matrix_rowblock_long_download": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
